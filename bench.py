@@ -6,7 +6,12 @@ func="mean", engine="hip" — one "step" = one full grouped mean over the
 resident shard (fused factorize+sum+count kernel -> combine -> finalize),
 inputs already in HBM when the timed region starts.
 
-Run:  python bench.py [--gpus N] [--steps K] [--warmup W]
+Run:  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds what needs runs of its own: the per-kernel HIP-event roofline
+(with the committed PMC traffic figure) and the CPU baseline leg.
+--dump-outputs DIR writes what the last timed step returned (result and
+groups) as DIR/<name>.npy.
 N>1 is launched by the driver via torch.distributed.run (one rank per GPU,
 RCCL); each rank holds its own 1e9-row shard (weak scaling) and the per-group
 partial bins are combined with one all-reduce per partial.
@@ -102,6 +107,28 @@ def read_traffic(config: str):
     return None
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # all dumped arrays together stay under 64 MB
+
+
+def dump_outputs(outdir: str, out: tuple) -> None:
+    """Write what the last timed step returned — (result, *groups), as the
+    caller of groupby_reduce receives them — to ``outdir/<name>.npy`` in
+    float32/float64. An array over its share of the size budget is cut to a
+    fixed, seeded sample of its flattened elements (same indices every run)."""
+    os.makedirs(outdir, exist_ok=True)
+    names = ["result"] + [f"groups_{i}" for i in range(len(out) - 1)]
+    share = DUMP_BUDGET_BYTES // len(out)
+    for name, a in zip(names, out):
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        keep = share // a.itemsize
+        if a.size > keep:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -111,6 +138,16 @@ def main():
     ap.add_argument("--ngroups", type=int, default=NGROUPS)
     ap.add_argument("--func", default="mean")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument(
+        "--full", action="store_true",
+        help="also measure what needs runs of its own: the HIP-event kernel "
+             "roofline (+ committed PMC traffic) and the CPU baseline leg",
+    )
+    ap.add_argument(
+        "--dump-outputs", metavar="DIR", default=None,
+        help="after the timed steps, write what the last one returned "
+             "(result, groups) as DIR/<name>.npy",
+    )
     ap.add_argument(
         "--no-graph", action="store_true",
         help="disable hipGraph step replay (auto-enabled at world 1 when the "
@@ -124,6 +161,8 @@ def main():
         help="BASELINE.json config to measure (default 2 = the headline 1e9-row/1e4-group mean)",
     )
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import flox_amd
     from flox_amd import aggregate_hip, core as fa_core
@@ -153,8 +192,7 @@ def main():
         cfg_extra = {"rows": n, "ngroups": ng, "func": func, "labels": "int64"}
 
         def step():
-            res, _ = flox_amd.groupby_reduce(vals, labels, func=func, expected_groups=expected)
-            return res
+            return flox_amd.groupby_reduce(vals, labels, func=func, expected_groups=expected)
     elif args.config == "3":
         n, ng = args.rows, 10_000_000
         func = "sum"
@@ -167,8 +205,7 @@ def main():
         cfg_extra = {"rows": n, "ngroups": ng, "func": func, "labels": "int64"}
 
         def step():
-            res, _ = flox_amd.groupby_reduce(vals, labels, func=func, expected_groups=expected)
-            return res
+            return flox_amd.groupby_reduce(vals, labels, func=func, expected_groups=expected)
     elif args.config == "4":
         n_t, y, x = 8760, 720, 1440
         func = args.func if args.func in ("sum", "mean", "var") else "mean"
@@ -183,8 +220,7 @@ def main():
         cfg_extra = {"shape": [n_t, y, x], "ngroups": 24, "func": func}
 
         def step():
-            res, _ = flox_amd.groupby_reduce(view, hours, func=func, expected_groups=expected)
-            return res
+            return flox_amd.groupby_reduce(view, hours, func=func, expected_groups=expected)
     else:  # config 5
         n = 100_000_000
         func = "nanmean"
@@ -199,10 +235,9 @@ def main():
         cfg_extra = {"rows": n, "grp_shape": [12, 180], "func": func}
 
         def step():
-            res, *_g = flox_amd.groupby_reduce(
+            return flox_amd.groupby_reduce(
                 vals, months, latbin, func=func, expected_groups=expected
             )
-            return res
 
     def barrier():
         if world > 1:
@@ -255,8 +290,8 @@ def main():
             torch.cuda.synchronize()
             eager_res = step()
             torch.cuda.synchronize()
-            gr = graph_res.to(torch.float64)
-            er = eager_res.to(torch.float64)
+            gr = graph_res[0].to(torch.float64)
+            er = eager_res[0].to(torch.float64)
             ok = bool(
                 torch.isclose(gr, er, rtol=1e-10, atol=1e-10, equal_nan=True)
                 .all().item()
@@ -292,8 +327,9 @@ def main():
             except Exception:
                 pass
 
-    # roofline instrumentation: HIP events around every fused-kernel launch
-    # on the launch stream (kernel + its O(ngroups) slab-combine tail)
+    # roofline instrumentation (--full only): HIP events around every
+    # fused-kernel launch on the launch stream (kernel + its O(ngroups)
+    # slab-combine tail)
     events = []
     orig = aggregate_hip.grouped_partials
     orig_cols = aggregate_hip.grouped_partials_cols
@@ -309,12 +345,13 @@ def main():
             return out
         return wrapper
 
-    aggregate_hip.grouped_partials = _timed(orig)
-    fa_core.grouped_partials = aggregate_hip.grouped_partials  # core binds the name
-    aggregate_hip.grouped_partials_cols = _timed(orig_cols)
-    fa_core.grouped_partials_cols = aggregate_hip.grouped_partials_cols
+    if args.full:
+        aggregate_hip.grouped_partials = _timed(orig)
+        fa_core.grouped_partials = aggregate_hip.grouped_partials  # core binds the name
+        aggregate_hip.grouped_partials_cols = _timed(orig_cols)
+        fa_core.grouped_partials_cols = aggregate_hip.grouped_partials_cols
 
-    if graph is not None:
+    if args.full and graph is not None:
         # graph replays bypass the python wrapper: collect the roofline
         # events from instrumented eager steps OUTSIDE the timed region
         for _ in range(min(3, args.steps)):
@@ -328,12 +365,13 @@ def main():
     if graph is not None:
         for _ in range(args.steps):
             graph.replay()
+        last = graph_res  # the captured step's outputs, rewritten by each replay
     else:
         for _ in range(args.steps):
-            step()
+            last = step()
     barrier()
     elapsed = time.perf_counter() - t0
-    if graph is not None:
+    if args.full and graph is not None:
         events = graph_events
     aggregate_hip.grouped_partials = orig
     fa_core.grouped_partials = orig
@@ -353,7 +391,7 @@ def main():
         total_bytes = bytes_per_step_per_gpu * world * args.steps
         value = total_bytes / elapsed / 1e9
         cpu = None
-        if args.config == "2" and not args.no_cpu_baseline:
+        if args.full and args.config == "2" and not args.no_cpu_baseline:
             cpu = cpu_baseline_leg(min(args.rows, 30_000_000), args.ngroups)
         out = {
             "metric": "grouped-reduce GB/s (input bytes/s) + fraction of HBM peak, 1e9 rows",
@@ -374,7 +412,9 @@ def main():
                 "parallelism": f"dp{world}" if world > 1 else "single",
                 "hipgraph": graph is not None,
             },
-            "roofline": {
+            "full": args.full,
+            # roofline and cpu_baseline take runs of their own: --full only
+            "roofline": None if not args.full else {
                 "bound": "hbm",
                 "achieved": round(achieved_gbps, 2) if achieved_gbps else None,
                 "peak": HBM_PEAK_GBPS,
@@ -384,6 +424,8 @@ def main():
             },
             "cpu_baseline": cpu,
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last)
         print(json.dumps(out), flush=True)
 
     if world > 1:

@@ -8,7 +8,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/pmc
 mkdir -p "$OUT"
 for CFG in 3 4 5; do
-  B="python $REPO/bench.py --config $CFG --steps 3 --warmup 1 --no-cpu-baseline"
+  B="python $REPO/bench.py --config $CFG --steps 3 --warmup 1 --full --no-cpu-baseline"
   rocprofv3 --pmc FETCH_SIZE -d "$OUT/c${CFG}_fetch" -- $B > /dev/null 2> "$OUT/c${CFG}_fetch.log"
   rocprofv3 --pmc WRITE_SIZE -d "$OUT/c${CFG}_write" -- $B > /dev/null 2> "$OUT/c${CFG}_write.log"
 done

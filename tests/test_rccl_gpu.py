@@ -100,7 +100,7 @@ def _worker2(rank, world, port, fail_q, ok_q):
             ok_q.put(("refused", f"{type(e).__name__}: {e}"))
             return
         import sys
-        sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+        sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
         import flox_amd
         from oracle import groupby_reduce as oracle_reduce
 
