@@ -18,7 +18,7 @@ _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfloxhip
 
 # fh_dtype / fh_ldtype / fh_opset / fh_flags — mirror include/floxhip.h
 F32, F64, I64, I32 = 0, 1, 2, 3
-L_I64, L_I32 = 0, 1
+L_I64, L_I32, L_U16 = 0, 1, 2
 SET_SUM_COUNT = 0
 SET_SUM_COUNT_PRESENT = 1
 SET_COUNT = 2
@@ -80,6 +80,8 @@ class FhCall(ctypes.Structure):
         ("nchunks", ctypes.c_int64),
         ("target", ctypes.c_void_p),
         ("row_offset", ctypes.c_int64),
+        # label-code cache: uint16[n] output of an emitting LDS-path call
+        ("emit_codes", ctypes.c_void_p),
     ]
 
 
@@ -120,7 +122,11 @@ def load_library():
     lib.fh_error_string.restype = ctypes.c_char_p
     lib.fh_version.argtypes = []
     lib.fh_version.restype = ctypes.c_int
-    if lib.fh_version() != 1:
+    lib.fh_query_path.argtypes = [ctypes.POINTER(FhCall)]
+    lib.fh_query_path.restype = ctypes.c_int
+    lib.fh_abi_revision.argtypes = []
+    lib.fh_abi_revision.restype = ctypes.c_int
+    if lib.fh_version() != 1 or lib.fh_abi_revision() < 2:
         raise RuntimeError("libfloxhip.so ABI version mismatch")
     _lib = lib
     return lib

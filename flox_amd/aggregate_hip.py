@@ -25,7 +25,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _ffi
+from . import _ffi, label_cache
 from ._ffi import (
     FLAG_SKIPNAN,
     SET_COUNT,
@@ -109,6 +109,7 @@ def grouped_partials(
     row_offset: int = 0,
     skipnan: bool = False,
     force_path: int = 0,
+    label_src: tuple | None = None,
 ) -> dict[str, torch.Tensor]:
     """One fused factorize+reduce pass. Returns per-group partial tensors.
 
@@ -117,6 +118,9 @@ def grouped_partials(
     means: f64[ngroups] for SET_SSD (var pass 2).
     target/row_offset: SET_IDXMIN/IDXMAX (arg-reductions, first/last).
     force_path: 0 auto, 1 LDS-binned, 2 global-atomic (testing).
+    label_src: the caller's own label tensor object(s) that labels (and
+        labels2) are flat views of — the label-code cache key
+        (label_cache.py). None = never cached.
     """
     lib = _ffi.load_library()
     _require_gpu_tensor(values, "values")
@@ -142,6 +146,7 @@ def grouped_partials(
         labels = torch.full((1,), -1, dtype=labels.dtype, device=labels.device)
         if labels2 is not None:
             labels2 = torch.full((1,), -1, dtype=labels2.dtype, device=labels2.device)
+        label_src = None
     assert values.ndim == 1 and labels.ndim == 1 and values.numel() == labels.numel()
     values = values.contiguous()
     labels = labels.contiguous()
@@ -163,12 +168,41 @@ def grouped_partials(
         # (overflow check / counting pre-pass), which would invalidate the
         # capture — restrict the C dispatcher to sync-free paths
         c.flags |= _ffi.FLAG_NO_HOST_SYNC
+    c.n = values.numel()
+    c.ngroups = ngroups
+    # label-code cache (label_cache.py): only for calls the LDS-binned
+    # kernel will serve, and never while capturing (a graph's label buffer
+    # is a static input the user may refill; baked-in codes would go stale)
+    plan = None
+    if (
+        label_src is not None
+        and force_path == 0
+        and not torch.cuda.is_current_stream_capturing()
+        and label_cache.CACHE.enabled
+        and lib.fh_query_path(ctypes.byref(c)) == 1
+    ):
+        plan = label_cache.CACHE.acquire(
+            label_src, grp_shape if labels2 is not None else ngroups, c.n
+        )
+    if plan is not None and plan.action == label_cache.HIT:
+        cur = torch.cuda.current_stream(dev)
+        if plan.stream != cur:
+            cur.wait_event(plan.event)
+        # a u16 label is the final code, also for two-by
+        labels, labels2, grp_shape = plan.codes, None, None
+        c.ldtype = _ffi.L_U16
+    emit = None
+    if plan is not None and plan.action == label_cache.EMIT:
+        emit = torch.empty(c.n, dtype=torch.uint16, device=dev)
+        c.emit_codes = emit.data_ptr()
     # sorted-labels direct path at huge group counts: skips every scatter
     # pass (~44 -> 12 B/row). A 4K-pair sample rejects random labels for
     # ~20 us; the full O(n) verification only runs when the sample passes
-    # (the time-ordered layout this targets).
+    # (the time-ordered layout this targets). A cache hit is always the LDS
+    # path, so it also skips the probe and its host sync.
     if (
         labels2 is None
+        and c.ldtype != _ffi.L_U16
         and force_path == 0
         and ngroups >= 8192
         and values.numel() >= 1_000_000
@@ -180,8 +214,6 @@ def grouped_partials(
             ok = bool((labels[1:] >= labels[:-1]).all().item())
             if ok and bool((labels[0] >= 0).item()) and bool((labels[-1] < ngroups).item()):
                 c.flags |= _ffi.FLAG_SORTED_LABELS
-    c.n = values.numel()
-    c.ngroups = ngroups
     c.values = values.data_ptr()
     c.labels = labels.data_ptr()
     if labels2 is not None:
@@ -240,10 +272,16 @@ def grouped_partials(
 
     _ffi.check(lib.fh_grouped_reduce(ctypes.byref(c)))
     out["_path"] = c.path_used  # type: ignore[assignment]
+    if emit is not None:
+        # consumers on other streams wait on this event
+        cur = torch.cuda.current_stream(dev)
+        ev = torch.cuda.Event()
+        ev.record(cur)
+        label_cache.CACHE.publish(plan, emit, ev, cur)
     # keep tensors alive until the stream consumes them (torch caching allocator
     # ties lifetime to the stream via recorded events only for torch ops; we
     # record explicitly)
-    for t in (values, labels, labels2, means, target, scratch):
+    for t in (values, labels, labels2, means, target, scratch, emit):
         _record(t, torch.cuda.current_stream(dev))
     return out
 

@@ -772,11 +772,28 @@ def groupby_reduce(
     lead_folded = False
 
     if lead_M == 1:
+        # label-code cache key: the CALLER's by object(s) — `labels` is a
+        # fresh view on every call. Only direct codes that reach the kernel
+        # untouched qualify (searchsorted / bins / string factorizations are
+        # the follow-up: DESIGN.md)
+        label_src = None
+        if (
+            len(facs) <= 2
+            and all(f.direct for f in facs)
+            and all(isinstance(b, torch.Tensor) and bb is b for b, bb in zip(by, bys))
+            and labels is facs[0].codes
+            and (labels2 is facs[1].codes if len(facs) == 2 else labels2 is None)
+        ):
+            label_src = tuple(by)
+        # the keyword travels only when set: stand-ins for grouped_partials
+        # with the uncached signature keep working
+        cache_kw = {} if label_src is None else {"label_src": label_src}
+
         def run_set(op_set, skipnan, means=None, target=None):
             return grouped_partials(
                 op_set, vals, labels, ngroups, skipnan=skipnan,
                 labels2=labels2, grp_shape=grp_pair, means=means,
-                target=target, row_offset=shard_row_offset,
+                target=target, row_offset=shard_row_offset, **cache_kw,
             )
     else:
         # column path: grouped dims to the front, lead dims flattened as
@@ -1144,6 +1161,9 @@ def groupby_reduce(
             owner = valid & (local >= 0) & (local < n_local)
             gathered = torch.where(owner, vals[safe], torch.zeros((), dtype=vals.dtype, device=device))
             distributed.all_reduce_(gathered, "sum")
+        elif n_local == 0:
+            # no rows: every group is empty and takes the fill below
+            gathered = torch.zeros(idx.shape, dtype=vals.dtype, device=device)
         else:
             gathered = vals[safe]
         result = gathered

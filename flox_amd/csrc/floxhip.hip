@@ -216,14 +216,44 @@ __host__ __device__ BinLayout bin_layout(int bits, int64_t ngroups, int64_t cnt_
   return L;
 }
 
-/* ---- kernel 1: LDS-binned grouped reduce -------------------------------- */
-template <typename V, typename L, int OPS>
+/* streaming vector load of one Vec. Every input byte of the LDS kernel is
+ * read once. NT = nontemporal 16-byte loads: 4.4-5.5 % faster for the
+ * int64/int32-label forms (12 B/row), no difference for the u16-code form,
+ * which keeps plain loads (profiles/r03_label_cache.md). Vecs narrower
+ * than 16 B are loaded plainly either way. */
+template <typename VT, bool NT>
+__device__ __forceinline__ VT ld_vec(const void* p) {
+  if constexpr (NT && sizeof(VT) % 16 == 0) {
+    using u32x4 = uint32_t __attribute__((ext_vector_type(4)));
+    VT t;
+#pragma unroll
+    for (int j = 0; j < (int)(sizeof(VT) / 16); ++j) {
+      u32x4 r = __builtin_nontemporal_load((const u32x4*)p + j);
+      __builtin_memcpy((char*)&t + 16 * j, &r, 16);
+    }
+    return t;
+  } else {
+    return *reinterpret_cast<const VT*>(p);
+  }
+}
+
+constexpr uint32_t CODE_NONE = 0xFFFFu; /* u16 code of a row in no group */
+constexpr int U16_ROWS = 8;  /* rows per lane per iteration, u16-code form */
+constexpr int EMIT_ROWS = 4; /* rows per lane per iteration when emitting */
+
+/* ---- kernel 1: LDS-binned grouped reduce --------------------------------
+ * L = uint16_t: labels are precomputed final codes (CODE_NONE = no group,
+ * labels2 unused); each lane takes U16_ROWS rows per iteration so that every
+ * stream is still read with 16-byte loads (one for the codes, 32 or 64 B of
+ * values). EMIT: the int64/int32-label run also writes each row's final
+ * code to `emit` (EMIT_ROWS rows per lane, one 8-byte store). */
+template <typename V, typename L, int OPS, bool EMIT = false>
 __launch_bounds__(BLOCK_LDS) __global__ void k_reduce_lds(
     const V* __restrict__ values, const L* __restrict__ labels,
     const L* __restrict__ labels2, int64_t n, int64_t ngroups, int64_t g0,
     int64_t g1, const double* __restrict__ means,
     const V* __restrict__ target, int64_t row_offset, int skipnan,
-    char* __restrict__ slab, BinLayout lay) {
+    char* __restrict__ slab, BinLayout lay, uint16_t* __restrict__ emit) {
   using TR = Traits<V>;
   using Acc = typename TR::Acc;
   using SumT = typename std::conditional<
@@ -256,18 +286,20 @@ __launch_bounds__(BLOCK_LDS) __global__ void k_reduce_lds(
 
   const bool twolab = labels2 != nullptr;
 
-  auto process = [&](V v, int64_t l0raw, int64_t l1raw, int64_t row) {
+  /* returns the row's final code (CODE_NONE when it is in no group) */
+  auto process = [&](V v, int64_t l0raw, int64_t l1raw, int64_t row) -> uint32_t {
     uint64_t code;
     if (twolab) {
-      if ((uint64_t)l0raw >= (uint64_t)g0 || (uint64_t)l1raw >= (uint64_t)g1) return;
+      if ((uint64_t)l0raw >= (uint64_t)g0 || (uint64_t)l1raw >= (uint64_t)g1) return CODE_NONE;
       code = (uint64_t)l0raw * (uint64_t)g1 + (uint64_t)l1raw;
     } else {
-      if ((uint64_t)l0raw >= (uint64_t)ngroups) return;
+      if ((uint64_t)l0raw >= (uint64_t)ngroups) return CODE_NONE;
       code = (uint64_t)l0raw;
     }
+    const uint32_t rcode = (uint32_t)code;
     const bool vnan = TR::isnan_(v);
     if (OPS & B_PRESENT) s_present[code] = 1u;  /* benign write race: all store 1 */
-    if (vnan && skipnan) return;
+    if (vnan && skipnan) return rcode;
     if (OPS & B_SUM) acc_add(&s_sum[code], (Acc)v);
     if (IS_PROD) acc_mul(&s_sum[code], (Acc)v);
     if (OPS & B_SSD) {
@@ -299,27 +331,70 @@ __launch_bounds__(BLOCK_LDS) __global__ void k_reduce_lds(
         if (OPS & B_MAX) enc_max(&s_mm[code], TR::enc(v));
       }
     }
+    return rcode;
   };
 
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + tid;
-  const int64_t nvec = n / VEC;
-  for (int64_t i = gtid; i < nvec; i += stride) {
-    Vec<V, VEC> vv = *reinterpret_cast<const Vec<V, VEC>*>(values + i * VEC);
-    Vec<L, VEC> lv = *reinterpret_cast<const Vec<L, VEC>*>(labels + i * VEC);
-    if (twolab) {
-      Vec<L, VEC> lv2 = *reinterpret_cast<const Vec<L, VEC>*>(labels2 + i * VEC);
+  if constexpr (std::is_same<L, uint16_t>::value) {
+    /* compact codes: one 16-B code load + U16_ROWS values per lane. The
+     * sentinel fails the bounds check in process() like any other
+     * out-of-range label. */
+    static_assert(!EMIT, "u16 codes are never re-emitted");
+    const int64_t nvec = n / U16_ROWS;
+    for (int64_t i = gtid; i < nvec; i += stride) {
+      const int64_t r0 = i * U16_ROWS;
+      Vec<uint16_t, U16_ROWS> cv = ld_vec<Vec<uint16_t, U16_ROWS>, false>(labels + r0);
+      Vec<V, VEC> vv[U16_ROWS / VEC];
 #pragma unroll
-      for (int k = 0; k < VEC; ++k)
-        process(vv.v[k], (int64_t)lv.v[k], (int64_t)lv2.v[k], i * VEC + k);
-    } else {
+      for (int j = 0; j < U16_ROWS / VEC; ++j)
+        vv[j] = ld_vec<Vec<V, VEC>, false>(values + r0 + j * VEC);
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) process(vv.v[k], (int64_t)lv.v[k], 0, i * VEC + k);
+      for (int k = 0; k < U16_ROWS; ++k)
+        process(vv[k / VEC].v[k % VEC], (int64_t)cv.v[k], 0, r0 + k);
     }
-  }
-  /* tail */
-  for (int64_t i = nvec * VEC + gtid; i < n; i += stride) {
-    process(values[i], (int64_t)labels[i], twolab ? (int64_t)labels2[i] : 0, i);
+    for (int64_t i = nvec * U16_ROWS + gtid; i < n; i += stride)
+      process(values[i], (int64_t)labels[i], 0, i);
+  } else if constexpr (EMIT) {
+    const int64_t nvec = n / EMIT_ROWS;
+    for (int64_t i = gtid; i < nvec; i += stride) {
+      const int64_t r0 = i * EMIT_ROWS;
+      Vec<V, VEC> vv[EMIT_ROWS / VEC];
+#pragma unroll
+      for (int j = 0; j < EMIT_ROWS / VEC; ++j)
+        vv[j] = ld_vec<Vec<V, VEC>, true>(values + r0 + j * VEC);
+      Vec<L, EMIT_ROWS> lv = ld_vec<Vec<L, EMIT_ROWS>, true>(labels + r0);
+      Vec<L, EMIT_ROWS> lv2 = lv;
+      if (twolab) lv2 = ld_vec<Vec<L, EMIT_ROWS>, true>(labels2 + r0);
+      Vec<uint16_t, EMIT_ROWS> cv;
+#pragma unroll
+      for (int k = 0; k < EMIT_ROWS; ++k)
+        cv.v[k] = (uint16_t)process(vv[k / VEC].v[k % VEC], (int64_t)lv.v[k],
+                                    (int64_t)lv2.v[k], r0 + k);
+      *reinterpret_cast<Vec<uint16_t, EMIT_ROWS>*>(emit + r0) = cv;
+    }
+    for (int64_t i = nvec * EMIT_ROWS + gtid; i < n; i += stride)
+      emit[i] = (uint16_t)process(values[i], (int64_t)labels[i],
+                                  twolab ? (int64_t)labels2[i] : 0, i);
+  } else {
+    const int64_t nvec = n / VEC;
+    for (int64_t i = gtid; i < nvec; i += stride) {
+      Vec<V, VEC> vv = ld_vec<Vec<V, VEC>, true>(values + i * VEC);
+      Vec<L, VEC> lv = ld_vec<Vec<L, VEC>, true>(labels + i * VEC);
+      if (twolab) {
+        Vec<L, VEC> lv2 = ld_vec<Vec<L, VEC>, true>(labels2 + i * VEC);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k)
+          process(vv.v[k], (int64_t)lv.v[k], (int64_t)lv2.v[k], i * VEC + k);
+      } else {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) process(vv.v[k], (int64_t)lv.v[k], 0, i * VEC + k);
+      }
+    }
+    /* tail */
+    for (int64_t i = nvec * VEC + gtid; i < n; i += stride) {
+      process(values[i], (int64_t)labels[i], twolab ? (int64_t)labels2[i] : 0, i);
+    }
   }
 
   __syncthreads();
@@ -2118,75 +2193,14 @@ int launch_partition(fh_call* c, const PartPlan& pp) {
 
 /* ---- host-side dispatch -------------------------------------------------- */
 
+/* everything past the LDS-binned path: sorted-direct, bucket partition,
+ * global atomics (never instantiated for uint16 code labels) */
 template <typename V, typename L, int OPS>
-int launch_typed(fh_call* c) {
+int launch_beyond_lds(fh_call* c) {
   using TR = Traits<V>;
   hipStream_t stream = (hipStream_t)c->stream;
   const bool skipnan = (c->flags & FH_SKIPNAN) != 0;
-  BinLayout lay = bin_layout<V>(OPS, c->ngroups, 4);
-
-  if (OPS & B_ARGROW) {
-    /* pair-payload arg-reductions exist only on the partition path (which
-     * host-syncs, so also refused during capture — callers use the
-     * two-pass form there) */
-    if (c->flags & (FH_FORCE_LDS | FH_FORCE_ATOMIC | FH_NO_HOST_SYNC))
-      return 11;
-    PartPlan pp = part_plan<V>(c);
-    if (!pp.feasible || c->scratch_bytes < pp.bytes) return 11;
-    return launch_partition<V, L, OPS>(c, pp);
-  }
-
-  bool use_lds = lay.bytes <= LDS_MAX;
-  if (c->flags & FH_FORCE_ATOMIC) use_lds = false;
-  if (c->flags & FH_FORCE_LDS) {
-    if (lay.bytes > LDS_MAX) return 2; /* cannot honor */
-    use_lds = true;
-  }
-
-  if (use_lds) {
-    int blocks_per_cu = lay.bytes * 2 <= LDS_MAX ? 2 : 1;
-    int nblocks = NUM_CU * blocks_per_cu;
-    /* do not launch more blocks than there is work or scratch for */
-    int64_t work_blocks = (c->n + BLOCK_LDS - 1) / BLOCK_LDS;
-    if (work_blocks < nblocks) nblocks = (int)(work_blocks > 0 ? work_blocks : 1);
-    if ((int64_t)nblocks * lay.bytes > c->scratch_bytes) return 3;
-
-    auto kern = k_reduce_lds<V, L, OPS>;
-    FH_CHECK(hipFuncSetAttribute((const void*)kern,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)lay.bytes));
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(BLOCK_LDS), lay.bytes, stream,
-                       (const V*)c->values, (const L*)c->labels,
-                       (const L*)c->labels2, c->n, c->ngroups, c->g0, c->g1,
-                       c->means, (const V*)c->target, c->row_offset,
-                       (int)skipnan, (char*)c->scratch, lay);
-    FH_CHECK(hipGetLastError());
-    int cb = (int)((c->ngroups + 255) / 256);
-    /* fill the chip even for tiny group counts: split the slab-block fold */
-    int S = 1;
-    if (c->ngroups < 65536) {
-      S = (int)((524288 + c->ngroups - 1) / c->ngroups);
-      if (S > nblocks) S = nblocks;
-      if (S < 1) S = 1;
-    }
-    if (S > 1) {
-      int rc = init_outs<V, OPS>(c, c->ngroups, stream);
-      if (rc) return rc;
-    }
-    hipLaunchKernelGGL((k_combine<V, OPS>), dim3(cb, S), dim3(256), 0, stream,
-                       (const char*)c->scratch, nblocks, c->ngroups, lay,
-                       c->out_sum, c->out_count, c->out_present, c->out_min,
-                       c->out_max, c->out_nanflag);
-    FH_CHECK(hipGetLastError());
-    if (S > 1 && (OPS & (B_MIN | B_MAX))) {
-      hipLaunchKernelGGL((k_decode<V, OPS>), dim3(cb), dim3(256), 0, stream,
-                         c->ngroups, c->out_min, c->out_max, c->out_count,
-                         c->out_present);
-      FH_CHECK(hipGetLastError());
-    }
-    c->path_used = 1;
-    return 0;
-  }
+  if (c->emit_codes) return 13; /* codes are emitted by the LDS kernel only */
 
   /* sorted-labels direct path: skip every scatter pass — each bucket's rows
    * are already a contiguous range of the original arrays */
@@ -2286,6 +2300,95 @@ int launch_typed(fh_call* c) {
   return 0;
 }
 
+template <typename V, typename L, int OPS>
+int launch_typed(fh_call* c) {
+  hipStream_t stream = (hipStream_t)c->stream;
+  const bool skipnan = (c->flags & FH_SKIPNAN) != 0;
+  BinLayout lay = bin_layout<V>(OPS, c->ngroups, 4);
+  constexpr bool U16 = std::is_same<L, uint16_t>::value;
+
+  if constexpr (U16) {
+    /* compact codes exist for the LDS-binned kernel only */
+    if ((OPS & B_ARGROW) || c->labels2 || c->emit_codes ||
+        c->ngroups >= (int64_t)CODE_NONE || lay.bytes > LDS_MAX ||
+        (c->flags & FH_FORCE_ATOMIC))
+      return 12;
+  } else if (OPS & B_ARGROW) {
+    /* pair-payload arg-reductions exist only on the partition path (which
+     * host-syncs, so also refused during capture — callers use the
+     * two-pass form there) */
+    if (c->flags & (FH_FORCE_LDS | FH_FORCE_ATOMIC | FH_NO_HOST_SYNC))
+      return 11;
+    PartPlan pp = part_plan<V>(c);
+    if (!pp.feasible || c->scratch_bytes < pp.bytes) return 11;
+    return launch_partition<V, L, OPS>(c, pp);
+  }
+
+  bool use_lds = lay.bytes <= LDS_MAX;
+  if (c->flags & FH_FORCE_ATOMIC) use_lds = false;
+  if (c->flags & FH_FORCE_LDS) {
+    if (lay.bytes > LDS_MAX) return 2; /* cannot honor */
+    use_lds = true;
+  }
+
+  if (use_lds) {
+    int blocks_per_cu = lay.bytes * 2 <= LDS_MAX ? 2 : 1;
+    int nblocks = NUM_CU * blocks_per_cu;
+    /* do not launch more blocks than there is work or scratch for */
+    const int64_t block_rows = (int64_t)BLOCK_LDS * (U16 ? U16_ROWS : 1);
+    int64_t work_blocks = (c->n + block_rows - 1) / block_rows;
+    if (work_blocks < nblocks) nblocks = (int)(work_blocks > 0 ? work_blocks : 1);
+    if ((int64_t)nblocks * lay.bytes > c->scratch_bytes) return 3;
+
+    auto kern = k_reduce_lds<V, L, OPS>;
+    if constexpr (!U16) {
+      if (c->emit_codes) {
+        if (c->ngroups >= (int64_t)CODE_NONE) return 13;
+        kern = k_reduce_lds<V, L, OPS, true>;
+      }
+    }
+    FH_CHECK(hipFuncSetAttribute((const void*)kern,
+                                 hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)lay.bytes));
+    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(BLOCK_LDS), lay.bytes, stream,
+                       (const V*)c->values, (const L*)c->labels,
+                       (const L*)c->labels2, c->n, c->ngroups, c->g0, c->g1,
+                       c->means, (const V*)c->target, c->row_offset,
+                       (int)skipnan, (char*)c->scratch, lay,
+                       (uint16_t*)c->emit_codes);
+    FH_CHECK(hipGetLastError());
+    int cb = (int)((c->ngroups + 255) / 256);
+    /* fill the chip even for tiny group counts: split the slab-block fold */
+    int S = 1;
+    if (c->ngroups < 65536) {
+      S = (int)((524288 + c->ngroups - 1) / c->ngroups);
+      if (S > nblocks) S = nblocks;
+      if (S < 1) S = 1;
+    }
+    if (S > 1) {
+      int rc = init_outs<V, OPS>(c, c->ngroups, stream);
+      if (rc) return rc;
+    }
+    hipLaunchKernelGGL((k_combine<V, OPS>), dim3(cb, S), dim3(256), 0, stream,
+                       (const char*)c->scratch, nblocks, c->ngroups, lay,
+                       c->out_sum, c->out_count, c->out_present, c->out_min,
+                       c->out_max, c->out_nanflag);
+    FH_CHECK(hipGetLastError());
+    if (S > 1 && (OPS & (B_MIN | B_MAX))) {
+      hipLaunchKernelGGL((k_decode<V, OPS>), dim3(cb), dim3(256), 0, stream,
+                         c->ngroups, c->out_min, c->out_max, c->out_count,
+                         c->out_present);
+      FH_CHECK(hipGetLastError());
+    }
+    c->path_used = 1;
+    return 0;
+  }
+  if constexpr (U16)
+    return 12; /* not reached: the guard above admits LDS-sized bins only */
+  else
+    return launch_beyond_lds<V, L, OPS>(c);
+}
+
 template <typename V, typename L>
 int dispatch_ops(fh_call* c) {
   switch (set_bits(c->op_set)) {
@@ -2307,12 +2410,16 @@ int dispatch_ops(fh_call* c) {
     case B_IDXMAX | B_CNT | B_PRESENT:
       return launch_typed<V, L, B_IDXMAX | B_CNT | B_PRESENT>(c);
     case B_MIN | B_CNT | B_PRESENT | B_NANFLAG | B_ARGROW:
-      if constexpr (sizeof(V) == 8)
+      if constexpr (std::is_same<L, uint16_t>::value)
+        return 12; /* partition path only: no compact-code form */
+      else if constexpr (sizeof(V) == 8)
         return launch_typed<V, L, B_MIN | B_CNT | B_PRESENT | B_NANFLAG | B_ARGROW>(c);
       else
         return 11; /* 4-byte dtypes pack (enc32,row32) keys instead */
     case B_MAX | B_CNT | B_PRESENT | B_NANFLAG | B_ARGROW:
-      if constexpr (sizeof(V) == 8)
+      if constexpr (std::is_same<L, uint16_t>::value)
+        return 12;
+      else if constexpr (sizeof(V) == 8)
         return launch_typed<V, L, B_MAX | B_CNT | B_PRESENT | B_NANFLAG | B_ARGROW>(c);
       else
         return 11;
@@ -2325,6 +2432,7 @@ int dispatch_label(fh_call* c) {
   switch (c->ldtype) {
     case FH_L_I64: return dispatch_ops<V, int64_t>(c);
     case FH_L_I32: return dispatch_ops<V, int32_t>(c);
+    case FH_L_U16: return dispatch_ops<V, uint16_t>(c);
     default: return 5;
   }
 }
@@ -2588,6 +2696,24 @@ int64_t fh_scratch_bytes(const fh_call* c) {
   return (int64_t)NUM_CU * blocks_per_cu * per_block;
 }
 
+int fh_query_path(const fh_call* c) {
+  if (!c) return -1;
+  const int bits = set_bits(c->op_set);
+  if (!bits) return -1;
+  int64_t per_block;
+  switch (c->vdtype) {
+    case FH_F32: per_block = bin_layout<float>(bits, c->ngroups, 4).bytes; break;
+    case FH_F64: per_block = bin_layout<double>(bits, c->ngroups, 4).bytes; break;
+    case FH_I64: per_block = bin_layout<int64_t>(bits, c->ngroups, 4).bytes; break;
+    case FH_I32: per_block = bin_layout<int32_t>(bits, c->ngroups, 4).bytes; break;
+    default: return -1;
+  }
+  /* mirrors launch_typed: arg-pair sets never bin in LDS, FORCE_ATOMIC
+   * wins over size, everything else is decided by the bins fitting */
+  if ((bits & B_ARGROW) || (c->flags & FH_FORCE_ATOMIC)) return 0;
+  return per_block <= LDS_MAX ? 1 : 0;
+}
+
 int fh_grouped_reduce(fh_call* c) {
   if (!c || !c->values || !c->labels) return 6;
   if (c->labels2 && c->g0 * c->g1 != c->ngroups) return 7;
@@ -2652,10 +2778,13 @@ const char* fh_error_string(int code) {
     case 8: return "FH_SET_SSD requires means";
     case 9: return "unknown value dtype";
     case 11: return "arg-pair reduction needs the bucket-partition path (8-byte dtype, n < 2^31, ngroups <= 2^24)";
+    case 12: return "uint16 code labels are valid on the LDS-binned path only (single code stream, bins within LDS; see fh_query_path)";
+    case 13: return "emit_codes needs the LDS-binned path and ngroups < 65535";
     default: return code >= 1000 ? hipGetErrorString((hipError_t)(code - 1000)) : "unknown error";
   }
 }
 
 int fh_version(void) { return 1; }
+int fh_abi_revision(void) { return 2; }
 
 }  /* extern "C" */

@@ -8,6 +8,10 @@ Supported options:
       tries the shard-aware sparse (touched-bin) exchange (distributed.py).
   sparse_combine_fraction: gathered-traffic fraction under which the sparse
       exchange engages (vs the dense all-reduce).
+  label_cache: False turns the label-code cache off (label_cache.py): every
+      call reads the caller's labels, as if each were a first sighting.
+  label_cache_entries: how many label tensors the cache tracks (LRU).
+  label_cache_bytes: byte budget for the cached uint16 codes (2 B/row).
 """
 
 from __future__ import annotations
@@ -18,12 +22,27 @@ OPTIONS = {
     "packed_arg_threshold": None,     # None = the measured default
     "sparse_combine_ngroups": None,
     "sparse_combine_fraction": None,
+    "label_cache": None,              # None = on
+    "label_cache_entries": None,
+    "label_cache_bytes": None,
+}
+
+_CACHE_FIELDS = {
+    "label_cache": "enabled",
+    "label_cache_entries": "max_entries",
+    "label_cache_bytes": "max_bytes",
 }
 
 
 def _apply(name, value):
-    from . import core, distributed
+    from . import core, distributed, label_cache
 
+    if name in _CACHE_FIELDS:
+        field = _CACHE_FIELDS[name]
+        old = getattr(label_cache.CACHE, field)
+        if value is not None:
+            label_cache.CACHE.configure(**{field: value})
+        return (name, old)
     if name == "packed_arg_threshold":
         old = core.PACKED_ARG_THRESHOLD
         if value is not None:
@@ -45,9 +64,11 @@ def _apply(name, value):
 
 
 def _restore(name, old):
-    from . import core, distributed
+    from . import core, distributed, label_cache
 
-    if name == "packed_arg_threshold":
+    if name in _CACHE_FIELDS:
+        label_cache.CACHE.configure(**{_CACHE_FIELDS[name]: old})
+    elif name == "packed_arg_threshold":
         core.PACKED_ARG_THRESHOLD = old
     elif name == "sparse_combine_ngroups":
         distributed.SPARSE_NGROUPS = old

@@ -31,7 +31,17 @@ extern "C" {
 /* value dtypes */
 enum fh_dtype { FH_F32 = 0, FH_F64 = 1, FH_I64 = 2, FH_I32 = 3 };
 /* label dtypes */
-enum fh_ldtype { FH_L_I64 = 0, FH_L_I32 = 1 };
+enum fh_ldtype {
+  FH_L_I64 = 0,
+  FH_L_I32 = 1,
+  /* precomputed compact codes (the label-code cache): a u16 label IS the
+   * final group code, also for 2-D groupbys (labels2 must be NULL), and
+   * 0xFFFF means "in no group" — the unsigned bounds check drops it, since
+   * ngroups stays below 65535 wherever the bins fit LDS. Valid only where
+   * the LDS-binned path is taken (fh_query_path() == 1); any other dispatch
+   * returns error 12. */
+  FH_L_U16 = 2,
+};
 
 /* Fused op sets: the per-group partials one pass produces.
  * (SUM accumulates float inputs in float64 — the numpy_groupies numerics
@@ -147,10 +157,22 @@ typedef struct fh_call {
    * and the global row offset of this shard (multi-GPU arg-reductions) */
   const void* target;
   int64_t row_offset;
+  /* optional (nullable): uint16[n], 16-byte aligned. When set on an
+   * int64/int32-label call that takes the LDS-binned path, the pass also
+   * writes each row's final code (labels[i], or labels[i]*g1 + labels2[i]
+   * for 2-D; 0xFFFF for a row in no group) — the FH_L_U16 input of later
+   * calls over the same labels. Error 13 on any other path. */
+  void* emit_codes;
 } fh_call;
 
 /* scratch requirement for this call (0 when the global-atomic path is used) */
 int64_t fh_scratch_bytes(const fh_call* c);
+
+/* which path fh_grouped_reduce would take for this call, without running
+ * it: 1 = LDS-binned, 0 = anything else (partition / sorted-direct /
+ * global-atomic), < 0 on a malformed call. Only op_set, vdtype, ngroups and
+ * flags are read. */
+int fh_query_path(const fh_call* c);
 
 /* run the fused grouped reduction; returns 0 on success */
 int fh_grouped_reduce(fh_call* c);
@@ -171,6 +193,10 @@ int fh_pack_argkeys(const void* values, int vdtype, int64_t n,
 
 const char* fh_error_string(int code);
 int fh_version(void);
+/* append-only revisions of fh_call within one fh_version: 2 added
+ * emit_codes, FH_L_U16 and fh_query_path. A caller built against revision R
+ * needs a library with fh_abi_revision() >= R. */
+int fh_abi_revision(void);
 
 #ifdef __cplusplus
 }
