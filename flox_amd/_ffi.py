@@ -38,6 +38,7 @@ FLAG_FORCE_LDS = 2
 FLAG_FORCE_ATOMIC = 4
 FLAG_SORTED_LABELS = 8
 FLAG_NO_HOST_SYNC = 16
+FINISH_NONE, FINISH_MEAN, FINISH_SUM, FINISH_COUNT = 0, 1, 2, 3
 
 VDTYPE_OF = {
     np.dtype("float32"): F32,
@@ -82,6 +83,13 @@ class FhCall(ctypes.Structure):
         ("row_offset", ctypes.c_int64),
         # label-code cache: uint16[n] output of an emitting LDS-path call
         ("emit_codes", ctypes.c_void_p),
+        # fused finish (fh_finish): result buffer instead of partials
+        ("finish", ctypes.c_int),
+        ("result_dtype", ctypes.c_int),
+        ("result", ctypes.c_void_p),
+        ("min_count", ctypes.c_int64),
+        ("has_fill", ctypes.c_int),
+        ("fill", ctypes.c_double),
     ]
 
 
@@ -126,7 +134,7 @@ def load_library():
     lib.fh_query_path.restype = ctypes.c_int
     lib.fh_abi_revision.argtypes = []
     lib.fh_abi_revision.restype = ctypes.c_int
-    if lib.fh_version() != 1 or lib.fh_abi_revision() < 2:
+    if lib.fh_version() != 1 or lib.fh_abi_revision() < 3:
         raise RuntimeError("libfloxhip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -110,6 +110,7 @@ def grouped_partials(
     skipnan: bool = False,
     force_path: int = 0,
     label_src: tuple | None = None,
+    finish: tuple | None = None,
 ) -> dict[str, torch.Tensor]:
     """One fused factorize+reduce pass. Returns per-group partial tensors.
 
@@ -121,6 +122,15 @@ def grouped_partials(
     label_src: the caller's own label tensor object(s) that labels (and
         labels2) are flat views of — the label-code cache key
         (label_cache.py). None = never cached.
+    finish: (mode, out_dtype, min_count, fill) — ask the combine kernel for
+        the finished aggregation instead of the partials. mode is one of
+        _ffi.FINISH_MEAN/SUM/COUNT and must be the one op_set feeds;
+        out_dtype is torch.float32/float64 (or int64 for sum/count); groups
+        with count < min_count (min_count > 0) or empty groups
+        (min_count == 0) receive `fill` unless it is None. Honored only
+        where the LDS-binned path serves the call: the return value then
+        holds "result" (and "_path") and no partial is allocated; otherwise
+        the partials come back as if finish were not given.
     """
     lib = _ffi.load_library()
     _require_gpu_tensor(values, "values")
@@ -236,6 +246,16 @@ def grouped_partials(
 
     members = _SET_MEMBERS[op_set]
     out: dict[str, torch.Tensor] = {}
+    if finish is not None and lib.fh_query_path(ctypes.byref(c)) == 1:
+        mode, out_dtype, min_count, fill = finish
+        out["result"] = torch.empty(ngroups, dtype=out_dtype, device=dev)
+        c.finish = mode
+        c.result_dtype = _TORCH_VDTYPE[out_dtype]
+        c.result = out["result"].data_ptr()
+        c.min_count = int(min_count)
+        c.has_fill = fill is not None
+        c.fill = float(fill) if fill is not None else 0.0
+        members = ()
     if "idx" in members:
         out["idx"] = torch.empty(ngroups, dtype=torch.int64, device=dev)
         c.out_sum = out["idx"].data_ptr()

@@ -40,6 +40,8 @@ from .aggregations import REDUCTIONS
 # from ~8e3 (1.09 vs 1.35; 2.6 vs 10.0 ms at 16e3). Tests lower this to
 # exercise the packed form at small n.
 PACKED_ARG_THRESHOLD = 6000
+# options.fused_finalize: mean/sum/count finished inside the combine kernel
+FUSED_FINALIZE = True
 
 # order-dependent reductions that run with leading array dims by folding the
 # lead index into the group codes (see groupby_reduce's lead-fold block)
@@ -157,6 +159,62 @@ def _cast_back_small(out_np: np.ndarray, func: str, small, fill_value=None) -> n
         # (reference aggregations.py:695-710); median preserves floating
         return out_np.astype(small)
     return out_np
+
+
+_FUSED_FUNCS = {
+    "mean": (_ffi.FINISH_MEAN, _ffi.SET_SUM_COUNT),
+    "nanmean": (_ffi.FINISH_MEAN, _ffi.SET_SUM_COUNT),
+    "sum": (_ffi.FINISH_SUM, _ffi.SET_SUM_COUNT_PRESENT),
+    "nansum": (_ffi.FINISH_SUM, _ffi.SET_SUM_COUNT_PRESENT),
+    "count": (_ffi.FINISH_COUNT, _ffi.SET_COUNT),
+}
+
+
+def _fused_finish(func, op_set, val_dtype, out_dtype, min_count_, fill_value):
+    """The `finish=` request that makes the combine kernel reproduce this
+    call's finalize (division, mask, fill, cast), or None where the torch
+    finalize must run: the two fill cases that inspect the mask on the host
+    (no fill with min_count > 0; a NaN fill into an integer result, which
+    promotes the dtype) and dtype pairs the kernel does not convert."""
+    if func not in _FUSED_FUNCS or _FUSED_FUNCS[func][1] != op_set:
+        return None
+    mode = _FUSED_FUNCS[func][0]
+    try:
+        t_out = _torch_dtype(out_dtype)
+    except Exception:
+        return None
+    float_out = t_out in (torch.float32, torch.float64)
+    if not float_out and (t_out != torch.int64 or mode == _ffi.FINISH_MEAN):
+        return None
+    if val_dtype not in (torch.float32, torch.float64, torch.int32, torch.int64):
+        return None
+    if val_dtype.is_floating_point and mode == _ffi.FINISH_SUM and not float_out:
+        return None  # f64 sums to an integer dtype: torch's cast rules apply
+    if min_count_ > 0:
+        fv = fill_value
+        if fv is None:
+            return None
+    else:
+        fv = fill_value if fill_value is not None else xrdtypes.fill_default(func, out_dtype)
+    if isinstance(fv, (bool, np.bool_)) or not isinstance(
+        fv, (int, float, np.integer, np.floating)
+    ):
+        return None
+    nan_fv = isinstance(fv, (float, np.floating)) and math.isnan(fv)
+    if nan_fv and not float_out:
+        return None
+    if nan_fv and mode != _ffi.FINISH_MEAN and not val_dtype.is_floating_point:
+        return None  # NaN into an integer sum/count promotes: torch finalize
+    # the kernel carries the fill as a double: it must survive the round trip
+    if not float_out and not (
+        float(fv) == int(fv) and int(float(fv)) == int(fv) and -(2**63) <= int(fv) < 2**63
+    ):
+        return None
+    if float_out and isinstance(fv, (int, np.integer)) and int(float(fv)) != int(fv):
+        return None
+    if min_count_ == 0 and nan_fv and mode == _ffi.FINISH_MEAN:
+        fv = None  # 0/0 already is the NaN the fill would write
+    return (mode, t_out, int(min_count_), None if fv is None else float(fv))
 
 
 def _coerce_by(b):
@@ -770,6 +828,7 @@ def groupby_reduce(
         )
     ddof = (finalize_kwargs or {}).get("ddof", 0)
     lead_folded = False
+    fused_done = False
 
     if lead_M == 1:
         # label-code cache key: the CALLER's by object(s) — `labels` is a
@@ -789,11 +848,12 @@ def groupby_reduce(
         # with the uncached signature keep working
         cache_kw = {} if label_src is None else {"label_src": label_src}
 
-        def run_set(op_set, skipnan, means=None, target=None):
+        def run_set(op_set, skipnan, means=None, target=None, finish=None):
+            fin_kw = {} if finish is None else {"finish": finish}
             return grouped_partials(
                 op_set, vals, labels, ngroups, skipnan=skipnan,
                 labels2=labels2, grp_shape=grp_pair, means=means,
-                target=target, row_offset=shard_row_offset, **cache_kw,
+                target=target, row_offset=shard_row_offset, **cache_kw, **fin_kw,
             )
     else:
         # column path: grouped dims to the front, lead dims flattened as
@@ -1211,12 +1271,21 @@ def groupby_reduce(
         if func in ("std", "nanstd"):
             result = torch.sqrt(result)
         counts_for_mask = counts
-        empty_mask = counts == 0
+        empty_mask = None  # count == 0, built only if a fill needs it
     else:
-        p = run_set(agg.op_set, agg.skipnan)
+        fin = None
+        if FUSED_FINALIZE and lead_M == 1 and not dist_on and ngroups > 0:
+            fin = _fused_finish(func, agg.op_set, vals.dtype, out_dtype, min_count_, fill_value)
+        p = run_set(agg.op_set, agg.skipnan) if fin is None else run_set(
+            agg.op_set, agg.skipnan, finish=fin
+        )
         if dist_on:
             distributed.combine_partials(p, agg.combine)
-        if func == "count":
+        if "result" in p:
+            # the combine kernel already divided, masked, filled and cast
+            result = p["result"]
+            fused_done = True
+        elif func == "count":
             result = p["count"]
             empty_mask = p["count"] == 0
             counts_for_mask = p["count"]
@@ -1226,7 +1295,7 @@ def groupby_reduce(
             counts_for_mask = p["count"]
         elif func in ("mean", "nanmean"):
             result = p["sum"].to(torch.float64) / p["count"]
-            empty_mask = p["count"] == 0
+            empty_mask = None  # count == 0, built only if a fill needs it
             counts_for_mask = p["count"]
         elif func in ("min", "nanmin", "max", "nanmax"):
             result = p["min" if "min" in p else "max"]
@@ -1259,7 +1328,9 @@ def groupby_reduce(
     # core.py:446-449 maybe_promote)
     t_out_dtype = _torch_dtype(out_dtype)
     is_float_out = torch.empty(0, dtype=t_out_dtype).is_floating_point()
-    if min_count_ > 0:
+    if fused_done:
+        pass
+    elif min_count_ > 0:
         mask = counts_for_mask < min_count_
         nan_fill = isinstance(fill_value, float) and math.isnan(fill_value)
         if fill_value is None or (nan_fill and not is_float_out):
@@ -1283,6 +1354,8 @@ def groupby_reduce(
             # 0/0 division already produced NaN exactly where the fill goes
             pass
         elif nan_fv and not is_float_out:
+            if empty_mask is None:
+                empty_mask = counts_for_mask == 0
             if bool(empty_mask.any().item()):
                 result = result.to(torch.float64)
                 t_out_dtype = torch.float64
@@ -1290,6 +1363,8 @@ def groupby_reduce(
                     empty_mask, torch.tensor(fv, dtype=t_out_dtype, device=device), result
                 )
         else:
+            if empty_mask is None:
+                empty_mask = counts_for_mask == 0
             result = result.to(t_out_dtype)
             result = torch.where(
                 empty_mask, torch.tensor(fv, dtype=t_out_dtype, device=device), result

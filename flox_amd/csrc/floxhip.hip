@@ -409,11 +409,10 @@ __launch_bounds__(BLOCK_LDS) __global__ void k_reduce_lds(
   }
 }
 
-/* ---- kernel 2: combine per-block slabs ----------------------------------
- * grid.y splits the slab-block range so small group counts still fill the
- * chip; with gridDim.y == 1 final bins are written directly (min/max
- * decoded inline), otherwise each chunk folds its share and merges into
- * memset-initialized bins with atomics (min/max stay encoded for k_decode). */
+/* ---- kernel 2: combine per-chunk slabs (column path) ---------------------
+ * one thread per bin folds every chunk's partial and writes the final bin
+ * (min/max decoded inline). The LDS-binned path folds its per-block slab
+ * with k_combine_tree below. */
 template <typename V, int OPS>
 __global__ void k_combine(const char* __restrict__ slab, int nblocks,
                           int64_t ngroups, BinLayout lay, void* out_sum,
@@ -428,13 +427,6 @@ __global__ void k_combine(const char* __restrict__ slab, int nblocks,
   constexpr bool IS_PROD = (OPS & B_PROD) != 0;
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= ngroups) return;
-  const int S = gridDim.y;
-  const int chunk = (nblocks + S - 1) / S;
-  const int b0 = blockIdx.y * chunk;
-  int b1 = b0 + chunk;
-  if (b1 > nblocks) b1 = nblocks;
-  if (b0 >= b1) return;
-
   SumT s = IS_PROD ? (SumT)1 : (SumT)0;
   if (OPS & B_IDXMIN) s = (SumT)INT64_MAX;
   if (OPS & B_IDXMAX) s = (SumT)(-1);
@@ -442,7 +434,7 @@ __global__ void k_combine(const char* __restrict__ slab, int nblocks,
   uint32_t p = 0, nf = 0;
   double w_sum = 0.0;
   Enc mn = (Enc)~(Enc)0, mx = (Enc)0;
-  for (int b = b0; b < b1; ++b) {
+  for (int b = 0; b < nblocks; ++b) {
     const char* blk = slab + (int64_t)b * lay.bytes;
     if (OPS & (B_SUM | B_SSD)) s += ((const SumT*)(blk + lay.sum_off))[g];
     if (OPS & B_WELFORD) {
@@ -476,34 +468,165 @@ __global__ void k_combine(const char* __restrict__ slab, int nblocks,
     }
     if (OPS & B_NANFLAG) nf |= ((const uint32_t*)(blk + lay.nanflag_off))[g];
   }
-  if (S == 1) {
-    const bool present = (OPS & B_PRESENT) ? (p != 0) : (c != 0);
-    if (OPS & B_WELFORD) {
-      const double total = (double)s - (c > 0 ? (w_sum * w_sum) / (double)c : 0.0);
-      ((double*)out_sum)[g] = c > 0 ? total : 0.0;
-      ((double*)out_min)[g] = w_sum;
-      out_count[g] = c;
-      return;
+  const bool present = (OPS & B_PRESENT) ? (p != 0) : (c != 0);
+  if (OPS & B_WELFORD) {
+    const double total = (double)s - (c > 0 ? (w_sum * w_sum) / (double)c : 0.0);
+    ((double*)out_sum)[g] = c > 0 ? total : 0.0;
+    ((double*)out_min)[g] = w_sum;
+    out_count[g] = c;
+    return;
+  }
+  if (OPS & (B_SUM | B_SSD | B_PROD | B_IDXMIN | B_IDXMAX)) ((SumT*)out_sum)[g] = s;
+  if (OPS & B_CNT) out_count[g] = c;
+  if (OPS & B_PRESENT) out_present[g] = p;
+  if (OPS & B_MIN) ((V*)out_min)[g] = present ? TR::dec(mn) : TR::pos_inf();
+  if (OPS & B_MAX) ((V*)out_max)[g] = present ? TR::dec(mx) : (V)-TR::pos_inf();
+  if (OPS & B_NANFLAG) out_nanflag[g] = nf;
+}
+
+/* ---- kernel 2b: tree combine of the LDS path's per-block slab -------------
+ * Thread block = CT_X consecutive groups (x) by CT_Y slab-block lanes (y).
+ * Thread (x, y) folds slab blocks y, y + CT_Y, ... of its group in registers
+ * (a wave reads two rows of CT_X consecutive bins: 256 B per f64 row), the
+ * CT_Y partials are folded through LDS in a fixed halving order, and the
+ * y == 0 threads write the final bins: no pre-zeroed outputs, no atomics, no
+ * decode pass, and a fold order that depends only on nblocks. CT_X = 32 keeps
+ * 1e4 groups at 313 blocks; a handful of groups is a single block.
+ *
+ * FIN != FIN_NONE finishes the aggregation in the same threads instead of
+ * writing partials: one result value per group, in fa.rdtype, with the fill
+ * where the group is masked (FinishArgs below). */
+constexpr int CT_X = 32;
+constexpr int CT_Y = 32;
+
+enum { FIN_NONE = 0, FIN_MEAN = FH_FINISH_MEAN, FIN_SUM = FH_FINISH_SUM,
+       FIN_COUNT = FH_FINISH_COUNT };
+
+__host__ __device__ constexpr int finish_of(int ops) {
+  return ops == (B_SUM | B_CNT)               ? FIN_MEAN
+         : ops == (B_SUM | B_CNT | B_PRESENT) ? FIN_SUM
+         : ops == B_CNT                       ? FIN_COUNT
+                                              : FIN_NONE;
+}
+
+struct FinishArgs {
+  void* result;
+  int rdtype;        /* fh_dtype of result: F32, F64 or I64 */
+  int has_fill;
+  int64_t min_count; /* masked = count < min_count, or empty when 0 */
+  double fill;
+};
+
+template <typename T>
+__device__ __forceinline__ void store_finished(const FinishArgs& fa, int64_t g,
+                                               T val, bool masked) {
+  switch (fa.rdtype) {
+    case FH_F32: ((float*)fa.result)[g] = masked ? (float)fa.fill : (float)val; break;
+    case FH_F64: ((double*)fa.result)[g] = masked ? fa.fill : (double)val; break;
+    default: ((int64_t*)fa.result)[g] = masked ? (int64_t)fa.fill : (int64_t)val; break;
+  }
+}
+
+template <typename V, int OPS, int FIN>
+__launch_bounds__(CT_X * CT_Y) __global__ void k_combine_tree(
+    const char* __restrict__ slab, int nblocks, int64_t ngroups, BinLayout lay,
+    void* out_sum, int64_t* out_count, uint32_t* out_present, void* out_min,
+    void* out_max, uint32_t* out_nanflag, FinishArgs fa) {
+  using TR = Traits<V>;
+  using Acc = typename TR::Acc;
+  using SumT = typename std::conditional<
+      (OPS & B_SSD) != 0, double,
+      typename std::conditional<(OPS & (B_IDXMIN | B_IDXMAX)) != 0, int64_t, Acc>::type>::type;
+  using Enc = typename TR::Enc;
+  constexpr bool IS_PROD = (OPS & B_PROD) != 0;
+  constexpr bool HAS_S = (OPS & (B_SUM | B_SSD | B_PROD | B_IDXMIN | B_IDXMAX)) != 0;
+  constexpr bool HAS_MM = (OPS & (B_MIN | B_MAX)) != 0;
+  constexpr bool HAS_FLAGS = (OPS & (B_PRESENT | B_NANFLAG)) != 0;
+  static_assert(FIN == FIN_NONE || FIN == finish_of(OPS), "finish mode/op set mismatch");
+  constexpr int NT = CT_X * CT_Y;
+
+  __shared__ SumT sh_s[HAS_S ? NT : 1];
+  __shared__ int64_t sh_c[(OPS & B_CNT) ? NT : 1];
+  __shared__ Enc sh_mm[HAS_MM ? NT : 1];
+  __shared__ uint32_t sh_f[HAS_FLAGS ? NT : 1]; /* bit 0 present, bit 1 nanflag */
+
+  const int tx = threadIdx.x, ty = threadIdx.y;
+  const int t = ty * CT_X + tx;
+  const int64_t g = (int64_t)blockIdx.x * CT_X + tx;
+  const bool live = g < ngroups;
+
+  SumT s = IS_PROD ? (SumT)1 : (SumT)0;
+  if (OPS & B_IDXMIN) s = (SumT)INT64_MAX;
+  if (OPS & B_IDXMAX) s = (SumT)(-1);
+  int64_t c = 0;
+  uint32_t f = 0;
+  Enc mm = (OPS & B_MIN) ? (Enc)~(Enc)0 : (Enc)0;
+  if (live) {
+#pragma unroll 4
+    for (int b = ty; b < nblocks; b += CT_Y) {
+      const char* blk = slab + (int64_t)b * lay.bytes;
+      if (HAS_S) {
+        const SumT x = ((const SumT*)(blk + lay.sum_off))[g];
+        if (OPS & (B_SUM | B_SSD)) s += x;
+        if (IS_PROD) s *= x;
+        if (OPS & B_IDXMIN) s = x < s ? x : s;
+        if (OPS & B_IDXMAX) s = x > s ? x : s;
+      }
+      if (OPS & B_CNT) c += (int64_t)((const uint32_t*)(blk + lay.cnt_off))[g];
+      if (OPS & B_PRESENT) f |= ((const uint32_t*)(blk + lay.present_off))[g] ? 1u : 0u;
+      if (OPS & B_NANFLAG) f |= ((const uint32_t*)(blk + lay.nanflag_off))[g] ? 2u : 0u;
+      if (HAS_MM) {
+        const Enc e = ((const Enc*)(blk + lay.minmax_off))[g];
+        if (OPS & B_MIN) mm = e < mm ? e : mm;
+        if (OPS & B_MAX) mm = e > mm ? e : mm;
+      }
     }
-    if (OPS & (B_SUM | B_SSD | B_PROD | B_IDXMIN | B_IDXMAX)) ((SumT*)out_sum)[g] = s;
+  }
+  if (HAS_S) sh_s[t] = s;
+  if (OPS & B_CNT) sh_c[t] = c;
+  if (HAS_MM) sh_mm[t] = mm;
+  if (HAS_FLAGS) sh_f[t] = f;
+  __syncthreads();
+  /* fixed-order fold over y: row y takes row y + h, h = CT_Y/2 .. 1 */
+#pragma unroll
+  for (int h = CT_Y / 2; h > 0; h >>= 1) {
+    if (ty < h) {
+      const int o = t + h * CT_X;
+      if (HAS_S) {
+        const SumT x = sh_s[o];
+        if (OPS & (B_SUM | B_SSD)) s += x;
+        if (IS_PROD) s *= x;
+        if (OPS & B_IDXMIN) s = x < s ? x : s;
+        if (OPS & B_IDXMAX) s = x > s ? x : s;
+        sh_s[t] = s;
+      }
+      if (OPS & B_CNT) { c += sh_c[o]; sh_c[t] = c; }
+      if (HAS_FLAGS) { f |= sh_f[o]; sh_f[t] = f; }
+      if (HAS_MM) {
+        const Enc e = sh_mm[o];
+        if (OPS & B_MIN) mm = e < mm ? e : mm;
+        if (OPS & B_MAX) mm = e > mm ? e : mm;
+        sh_mm[t] = mm;
+      }
+    }
+    __syncthreads();
+  }
+  if (ty != 0 || !live) return;
+
+  const uint32_t p = f & 1u, nf = (f >> 1) & 1u;
+  const bool present = (OPS & B_PRESENT) ? (p != 0) : (c != 0);
+  if constexpr (FIN != FIN_NONE) {
+    const bool masked = fa.has_fill && (fa.min_count > 0 ? c < fa.min_count : !present);
+    if constexpr (FIN == FIN_MEAN) store_finished(fa, g, (double)s / (double)c, masked);
+    if constexpr (FIN == FIN_SUM) store_finished(fa, g, s, masked);
+    if constexpr (FIN == FIN_COUNT) store_finished(fa, g, c, masked);
+  } else {
+    if (HAS_S) ((SumT*)out_sum)[g] = s;
     if (OPS & B_CNT) out_count[g] = c;
     if (OPS & B_PRESENT) out_present[g] = p;
-    if (OPS & B_MIN) ((V*)out_min)[g] = present ? TR::dec(mn) : TR::pos_inf();
-    if (OPS & B_MAX) ((V*)out_max)[g] = present ? TR::dec(mx) : (V)-TR::pos_inf();
+    if (OPS & B_MIN) ((V*)out_min)[g] = present ? TR::dec(mm) : TR::pos_inf();
+    if (OPS & B_MAX) ((V*)out_max)[g] = present ? TR::dec(mm) : (V)-TR::pos_inf();
     if (OPS & B_NANFLAG) out_nanflag[g] = nf;
-  } else {
-    if (OPS & (B_SUM | B_SSD)) acc_add((SumT*)out_sum + g, s);
-    if (IS_PROD) {
-      if (s != (SumT)1) acc_mul((SumT*)out_sum + g, s);
-    }
-    if (OPS & B_IDXMIN) idx_min((int64_t*)out_sum + g, (int64_t)s);
-    if (OPS & B_IDXMAX) idx_max((int64_t*)out_sum + g, (int64_t)s);
-    if ((OPS & B_CNT) && c)
-      atomicAdd(reinterpret_cast<unsigned long long*>(&out_count[g]), (unsigned long long)c);
-    if ((OPS & B_PRESENT) && p) out_present[g] = 1u;
-    if (OPS & B_MIN) enc_min(&((Enc*)out_min)[g], mn);
-    if (OPS & B_MAX) enc_max(&((Enc*)out_max)[g], mx);
-    if ((OPS & B_NANFLAG) && nf) out_nanflag[g] = 1u;
   }
 }
 
@@ -2307,6 +2430,17 @@ int launch_typed(fh_call* c) {
   BinLayout lay = bin_layout<V>(OPS, c->ngroups, 4);
   constexpr bool U16 = std::is_same<L, uint16_t>::value;
 
+  if (c->finish) {
+    /* a finish mode is served by the LDS path's combine only: refuse rather
+     * than hand back partials the caller did not allocate */
+    if (c->finish != finish_of(OPS) || lay.bytes > LDS_MAX ||
+        (c->flags & FH_FORCE_ATOMIC) || !c->result ||
+        (c->result_dtype != FH_F32 && c->result_dtype != FH_F64 &&
+         c->result_dtype != FH_I64) ||
+        (c->finish == FH_FINISH_MEAN && c->result_dtype == FH_I64))
+      return 14;
+  }
+
   if constexpr (U16) {
     /* compact codes exist for the LDS-binned kernel only */
     if ((OPS & B_ARGROW) || c->labels2 || c->emit_codes ||
@@ -2357,29 +2491,18 @@ int launch_typed(fh_call* c) {
                        (int)skipnan, (char*)c->scratch, lay,
                        (uint16_t*)c->emit_codes);
     FH_CHECK(hipGetLastError());
-    int cb = (int)((c->ngroups + 255) / 256);
-    /* fill the chip even for tiny group counts: split the slab-block fold */
-    int S = 1;
-    if (c->ngroups < 65536) {
-      S = (int)((524288 + c->ngroups - 1) / c->ngroups);
-      if (S > nblocks) S = nblocks;
-      if (S < 1) S = 1;
+    /* fold the slab; with a finish mode the same kernel writes the result */
+    const int cb = (int)((c->ngroups + CT_X - 1) / CT_X);
+    FinishArgs fa{c->result, c->result_dtype, c->has_fill, c->min_count, c->fill};
+    auto comb = k_combine_tree<V, OPS, FIN_NONE>;
+    if constexpr (finish_of(OPS) != FIN_NONE) {
+      if (c->finish) comb = k_combine_tree<V, OPS, finish_of(OPS)>;
     }
-    if (S > 1) {
-      int rc = init_outs<V, OPS>(c, c->ngroups, stream);
-      if (rc) return rc;
-    }
-    hipLaunchKernelGGL((k_combine<V, OPS>), dim3(cb, S), dim3(256), 0, stream,
+    hipLaunchKernelGGL(comb, dim3(cb), dim3(CT_X, CT_Y), 0, stream,
                        (const char*)c->scratch, nblocks, c->ngroups, lay,
                        c->out_sum, c->out_count, c->out_present, c->out_min,
-                       c->out_max, c->out_nanflag);
+                       c->out_max, c->out_nanflag, fa);
     FH_CHECK(hipGetLastError());
-    if (S > 1 && (OPS & (B_MIN | B_MAX))) {
-      hipLaunchKernelGGL((k_decode<V, OPS>), dim3(cb), dim3(256), 0, stream,
-                         c->ngroups, c->out_min, c->out_max, c->out_count,
-                         c->out_present);
-      FH_CHECK(hipGetLastError());
-    }
     c->path_used = 1;
     return 0;
   }
@@ -2734,6 +2857,7 @@ int fh_grouped_reduce_cols(fh_call* c) {
    * argsort permutation (int32) such that codes_sorted[i] = codes[perm[i]].
    * Outputs are (ngroups, m) group-major. */
   if (!c || !c->values || !c->labels || !c->perm) return 6;
+  if (c->finish) return 14;
   if (c->op_set == FH_SET_SSD && !c->means) return 8;
   switch (c->vdtype) {
     case FH_F32: return dispatch_cols_ops<float>(c);
@@ -2780,11 +2904,12 @@ const char* fh_error_string(int code) {
     case 11: return "arg-pair reduction needs the bucket-partition path (8-byte dtype, n < 2^31, ngroups <= 2^24)";
     case 12: return "uint16 code labels are valid on the LDS-binned path only (single code stream, bins within LDS; see fh_query_path)";
     case 13: return "emit_codes needs the LDS-binned path and ngroups < 65535";
+    case 14: return "finish mode needs the LDS-binned path, the op set it finishes (mean: SUM_COUNT, sum: SUM_COUNT_PRESENT, count: COUNT) and an f32/f64/i64 result buffer (see fh_query_path)";
     default: return code >= 1000 ? hipGetErrorString((hipError_t)(code - 1000)) : "unknown error";
   }
 }
 
 int fh_version(void) { return 1; }
-int fh_abi_revision(void) { return 2; }
+int fh_abi_revision(void) { return 3; }
 
 }  /* extern "C" */

@@ -12,6 +12,9 @@ Supported options:
       call reads the caller's labels, as if each were a first sighting.
   label_cache_entries: how many label tensors the cache tracks (LRU).
   label_cache_bytes: byte budget for the cached uint16 codes (2 B/row).
+  fused_finalize: False makes mean/sum/count return to per-group partials
+      finished by torch ops; on (the default) the combine kernel writes the
+      finished result where the LDS-binned path serves the call (core.py).
 """
 
 from __future__ import annotations
@@ -25,6 +28,7 @@ OPTIONS = {
     "label_cache": None,              # None = on
     "label_cache_entries": None,
     "label_cache_bytes": None,
+    "fused_finalize": None,           # None = on
 }
 
 _CACHE_FIELDS = {
@@ -48,6 +52,11 @@ def _apply(name, value):
         if value is not None:
             core.PACKED_ARG_THRESHOLD = int(value)
         return ("packed_arg_threshold", old)
+    if name == "fused_finalize":
+        old = core.FUSED_FINALIZE
+        if value is not None:
+            core.FUSED_FINALIZE = bool(value)
+        return ("fused_finalize", old)
     if name == "sparse_combine_ngroups":
         old = distributed.SPARSE_NGROUPS
         if value is not None:
@@ -70,6 +79,8 @@ def _restore(name, old):
         label_cache.CACHE.configure(**{_CACHE_FIELDS[name]: old})
     elif name == "packed_arg_threshold":
         core.PACKED_ARG_THRESHOLD = old
+    elif name == "fused_finalize":
+        core.FUSED_FINALIZE = old
     elif name == "sparse_combine_ngroups":
         distributed.SPARSE_NGROUPS = old
     elif name == "sparse_combine_fraction":

@@ -106,6 +106,19 @@ enum fh_flags {
                              * and counting pre-pass synchronize) */
 };
 
+/* finish modes: the LDS-binned path's combine kernel can write the finished
+ * aggregation (one value per group, in `result`) instead of the partials.
+ * Each mode belongs to one op set; masked groups receive `fill`:
+ * masked = has_fill && (min_count > 0 ? count < min_count : group empty),
+ * "empty" being present == 0 where the set has a present flag, else
+ * count == 0. Any call that cannot be served this way returns error 14. */
+enum fh_finish {
+  FH_FINISH_NONE = 0,
+  FH_FINISH_MEAN = 1,  /* FH_SET_SUM_COUNT: (double)sum / (double)count */
+  FH_FINISH_SUM = 2,   /* FH_SET_SUM_COUNT_PRESENT: the sum */
+  FH_FINISH_COUNT = 3, /* FH_SET_COUNT: the count */
+};
+
 typedef struct fh_call {
   int op_set;     /* fh_opset */
   int vdtype;     /* fh_dtype of `values` */
@@ -163,6 +176,17 @@ typedef struct fh_call {
    * for 2-D; 0xFFFF for a row in no group) — the FH_L_U16 input of later
    * calls over the same labels. Error 13 on any other path. */
   void* emit_codes;
+  /* finish mode (fh_finish; 0 = write partials as above). When set, none of
+   * the out_* buffers is touched: `result` ([ngroups] of result_dtype, an
+   * fh_dtype: FH_F32/FH_F64 for mean, those or FH_I64 for sum/count)
+   * receives the value converted with a plain C cast, or `fill` cast the
+   * same way where the group is masked. */
+  int finish;
+  int result_dtype;
+  void* result;
+  int64_t min_count;
+  int has_fill;
+  double fill;
 } fh_call;
 
 /* scratch requirement for this call (0 when the global-atomic path is used) */
@@ -194,7 +218,7 @@ int fh_pack_argkeys(const void* values, int vdtype, int64_t n,
 const char* fh_error_string(int code);
 int fh_version(void);
 /* append-only revisions of fh_call within one fh_version: 2 added
- * emit_codes, FH_L_U16 and fh_query_path. A caller built against revision R
+ * emit_codes, FH_L_U16 and fh_query_path; 3 added the finish fields. A caller built against revision R
  * needs a library with fh_abi_revision() >= R. */
 int fh_abi_revision(void);
 
