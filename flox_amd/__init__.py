@@ -12,7 +12,7 @@ from .aggregations import (  # noqa: F401
     CustomAggregation,
     generic_aggregate,
 )
-from .core import groupby_reduce  # noqa: F401
+from .core import groupby_reduce, groupby_reduce_many  # noqa: F401
 from .label_cache import clear_label_cache, label_cache_stats  # noqa: F401
 from .options import OPTIONS, set_options  # noqa: F401
 from .scan import groupby_scan  # noqa: F401

@@ -33,6 +33,7 @@ SET_IDXMAX = 10
 SET_WELFORD = 11
 SET_ARGMIN_PAIR = 12
 SET_ARGMAX_PAIR = 13
+SET_SUMMARY = 14
 FLAG_SKIPNAN = 1
 FLAG_FORCE_LDS = 2
 FLAG_FORCE_ATOMIC = 4
@@ -90,6 +91,8 @@ class FhCall(ctypes.Structure):
         ("min_count", ctypes.c_int64),
         ("has_fill", ctypes.c_int),
         ("fill", ctypes.c_double),
+        # SET_SUMMARY: f64[ngroups] sum of squared deviations about the mean
+        ("out_ssd", ctypes.c_void_p),
     ]
 
 
@@ -134,7 +137,7 @@ def load_library():
     lib.fh_query_path.restype = ctypes.c_int
     lib.fh_abi_revision.argtypes = []
     lib.fh_abi_revision.restype = ctypes.c_int
-    if lib.fh_version() != 1 or lib.fh_abi_revision() < 3:
+    if lib.fh_version() != 1 or lib.fh_abi_revision() < 4:
         raise RuntimeError("libfloxhip.so ABI version mismatch")
     _lib = lib
     return lib

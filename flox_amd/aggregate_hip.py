@@ -69,6 +69,9 @@ _SET_MEMBERS = {
     # idx = int64 row (INT64_MAX empty), min/max = the decoded extremum
     _ffi.SET_ARGMIN_PAIR: ("idx", "count", "present", "min", "nanflag"),
     _ffi.SET_ARGMAX_PAIR: ("idx", "count", "present", "max", "nanflag"),
+    # one pass for the whole sum/mean/var/std/min/max/count family (LDS path
+    # only; NaN rows touch nothing but nanflag; ssd = f64 M2 about the mean)
+    _ffi.SET_SUMMARY: ("sum", "count", "present", "min", "max", "nanflag", "ssd"),
 }
 
 IDX_SENTINEL_MIN = (1 << 63) - 1  # untouched IDXMIN bin
@@ -96,6 +99,19 @@ def _require_gpu_tensor(t: torch.Tensor, name: str) -> None:
         )
 
 
+def summary_fits(value_dtype: torch.dtype, ngroups: int) -> bool:
+    """Whether SET_SUMMARY can serve this dtype and group count: the set
+    exists on the LDS-binned path only, and the library knows its bin
+    layout (fh_query_path)."""
+    if value_dtype not in _TORCH_VDTYPE or ngroups <= 0:
+        return False
+    c = FhCall()
+    c.op_set = _ffi.SET_SUMMARY
+    c.vdtype = _TORCH_VDTYPE[value_dtype]
+    c.ngroups = ngroups
+    return _ffi.load_library().fh_query_path(ctypes.byref(c)) == 1
+
+
 def grouped_partials(
     op_set: int,
     values: torch.Tensor,
@@ -117,6 +133,11 @@ def grouped_partials(
     values, labels: contiguous 1-D CUDA tensors of equal length.
     labels2/grp_shape: fused 2-D groupby (reference factorize.py:102-108).
     means: f64[ngroups] for SET_SSD (var pass 2).
+    SET_SUMMARY: every partial of the sum/mean/var/std/min/max/count family
+        in one pass ("ssd" = f64 sum of squared deviations about the mean).
+        NaN rows only set "nanflag" whatever skipnan says (pass True);
+        "present" is count > 0 or nanflag. LDS-binned path only: check
+        summary_fits() first, anything else is an error.
     target/row_offset: SET_IDXMIN/IDXMAX (arg-reductions, first/last).
     force_path: 0 auto, 1 LDS-binned, 2 global-atomic (testing).
     label_src: the caller's own label tensor object(s) that labels (and
@@ -146,6 +167,7 @@ def grouped_partials(
             "min": torch.empty(0, dtype=values.dtype, device=dev0),
             "max": torch.empty(0, dtype=values.dtype, device=dev0),
             "nanflag": torch.empty(0, dtype=torch.int32, device=dev0),
+            "ssd": torch.empty(0, dtype=torch.float64, device=dev0),
         }
         return {k: empty[k] for k in _SET_MEMBERS[op_set]}
     if values.numel() == 0:
@@ -279,6 +301,9 @@ def grouped_partials(
     if "nanflag" in members:
         out["nanflag"] = torch.empty(ngroups, dtype=torch.int32, device=dev)
         c.out_nanflag = out["nanflag"].data_ptr()
+    if "ssd" in members:
+        out["ssd"] = torch.empty(ngroups, dtype=torch.float64, device=dev)
+        c.out_ssd = out["ssd"].data_ptr()
 
     nscratch = lib.fh_scratch_bytes(ctypes.byref(c))
     if nscratch < 0:

@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import _ffi, distributed, xrdtypes
-from .aggregate_hip import grouped_partials, grouped_partials_cols
+from .aggregate_hip import grouped_partials, grouped_partials_cols, summary_fits
 from .aggregations import REDUCTIONS
 
 # arg-reductions switch from the two-pass (extremum, then index-match) form to
@@ -42,6 +42,13 @@ from .aggregations import REDUCTIONS
 PACKED_ARG_THRESHOLD = 6000
 # options.fused_finalize: mean/sum/count finished inside the combine kernel
 FUSED_FINALIZE = True
+# options.fused_many: groupby_reduce_many serves these names from one
+# SET_SUMMARY pass where the call is eligible (see _ManyCall)
+FUSED_MANY = True
+FUSED_MANY_FUNCS = frozenset((
+    "count", "sum", "nansum", "mean", "nanmean", "var", "nanvar", "std",
+    "nanstd", "min", "nanmin", "max", "nanmax",
+))
 
 # order-dependent reductions that run with leading array dims by folding the
 # lead index into the group codes (see groupby_reduce's lead-fold block)
@@ -217,6 +224,53 @@ def _fused_finish(func, op_set, val_dtype, out_dtype, min_count_, fill_value):
     return (mode, t_out, int(min_count_), None if fv is None else float(fv))
 
 
+class _ManyCall:
+    """What the groupby_reduce calls made by one groupby_reduce_many share:
+    the factorization, the SET_SUMMARY partials (gathered by the first func
+    that needs a kernel pass) and the sort=False group order. `eligible` is
+    decided once, by the first call that reaches the 1-D engine."""
+
+    def __init__(self):
+        self.facs = None
+        self.eligible = None
+        self.partials = None
+        self.orders = {}
+
+
+# set by groupby_reduce_many for the duration of its groupby_reduce calls
+_MANY: _ManyCall | None = None
+
+
+def _from_summary(S, op_set, skipnan):
+    """The partials `op_set` would have produced, derived from the
+    NaN-skipping SET_SUMMARY partials S. Without skipnan a NaN row poisons
+    the sums (as it does in the kernels); min/max carry nanflag and the
+    finalize applies it."""
+    poison = None
+    if not skipnan and S["sum"].dtype.is_floating_point:
+        poison = S["nanflag"] != 0
+
+    def nanned(t):
+        return t if poison is None else torch.where(poison, torch.full_like(t, float("nan")), t)
+
+    if op_set == _ffi.SET_SSD:
+        return {"sum": nanned(S["ssd"])}
+    if op_set == _ffi.SET_SUM_COUNT:
+        return {"sum": nanned(S["sum"]), "count": S["count"]}
+    if op_set == _ffi.SET_SUM_COUNT_PRESENT:
+        return {"sum": nanned(S["sum"]), "count": S["count"], "present": S["present"]}
+    if op_set == _ffi.SET_COUNT:
+        return {"count": S["count"]}
+    if op_set in (_ffi.SET_MIN_FULL, _ffi.SET_MAX_FULL):
+        k = "min" if op_set == _ffi.SET_MIN_FULL else "max"
+        return {k: S[k], "count": S["count"], "present": S["present"],
+                "nanflag": S["nanflag"]}
+    if op_set in (_ffi.SET_MIN_COUNT, _ffi.SET_MAX_COUNT):
+        k = "min" if op_set == _ffi.SET_MIN_COUNT else "max"
+        return {k: S[k], "count": S["count"]}
+    raise NotImplementedError(f"op set {op_set} from summary partials")  # pragma: no cover
+
+
 def _coerce_by(b):
     # by / expected arrays in dtypes torch cannot ingest (u16/u32/i8/f16...)
     # carry the same information as int64/f32 - convert before the device
@@ -234,6 +288,15 @@ def _coerce_by(b):
 # outlive every replay (the graph re-executes the copy from the same host
 # address) — pin them here while capturing
 _CAPTURE_KEEPALIVE: list = []
+
+
+def _fill_scalar(fv, dtype, device, like: torch.Tensor) -> torch.Tensor:
+    """0-dim fill tensor for a where() over `like`. torch.tensor copies from
+    host memory, which a stream under hipGraph capture cannot do: there the
+    value is written by a fill kernel instead."""
+    if like.is_cuda and torch.cuda.is_current_stream_capturing():
+        return torch.full((), fv, dtype=dtype, device=device)
+    return torch.tensor(fv, dtype=dtype, device=device)
 
 
 def _keepalive_if_capturing(t: torch.Tensor) -> torch.Tensor:
@@ -517,6 +580,8 @@ def groupby_reduce(
     if func not in REDUCTIONS:
         raise NotImplementedError(f"reduction {func!r}")
     agg = REDUCTIONS[func]
+    many = _MANY  # the enclosing groupby_reduce_many call, if any
+    many_served = False
 
     if not torch.cuda.is_available():
         raise RuntimeError("flox_amd.groupby_reduce requires a GPU (engine='hip')")
@@ -736,14 +801,18 @@ def groupby_reduce(
         raise ValueError("isbin=True requires expected_groups (the bin edges)")
 
     isbins = isbin if isinstance(isbin, (tuple, list)) else (isbin,) * nby
-    facs = [
-        _factorize_strings_host(b.reshape(-1), e, sort, device)
-        if isinstance(b, np.ndarray)
-        else _factorize_bins(b.reshape(-1), e, dt_by=dtb)
-        if ib
-        else _factorize_device(b.reshape(-1), e, sort, dt_by=dtb)
-        for b, e, ib, dtb in zip(bys, expected_groups, isbins, by_dts)
-    ]
+    facs = many.facs if many is not None else None
+    if facs is None:
+        facs = [
+            _factorize_strings_host(b.reshape(-1), e, sort, device)
+            if isinstance(b, np.ndarray)
+            else _factorize_bins(b.reshape(-1), e, dt_by=dtb)
+            if ib
+            else _factorize_device(b.reshape(-1), e, sort, dt_by=dtb)
+            for b, e, ib, dtb in zip(bys, expected_groups, isbins, by_dts)
+        ]
+        if many is not None:
+            many.facs = facs
     grp_shape = tuple(f.ngroups for f in facs)
     ngroups = math.prod(grp_shape)
     labels, labels2, grp_pair = _combined_codes(facs)
@@ -855,6 +924,25 @@ def groupby_reduce(
                 labels2=labels2, grp_shape=grp_pair, means=means,
                 target=target, row_offset=shard_row_offset, **cache_kw, **fin_kw,
             )
+
+        if many is not None:
+            if many.eligible is None:
+                many.eligible = (
+                    not dist_on
+                    and dt_dtype is None
+                    and vals.numel() > 0
+                    and summary_fits(vals.dtype, ngroups)
+                )
+            if many.eligible and func in FUSED_MANY_FUNCS:
+                # every pass this func asks for is answered from the one
+                # summary pass; the finalize below runs unchanged
+                many_served = True
+                run_direct = run_set
+
+                def run_set(op_set, skipnan, means=None, target=None, finish=None):
+                    if many.partials is None:
+                        many.partials = run_direct(_ffi.SET_SUMMARY, True)
+                    return _from_summary(many.partials, op_set, skipnan)
     else:
         # column path: grouped dims to the front, lead dims flattened as
         # columns (a zero-copy view when the caller's layout is
@@ -1274,7 +1362,7 @@ def groupby_reduce(
         empty_mask = None  # count == 0, built only if a fill needs it
     else:
         fin = None
-        if FUSED_FINALIZE and lead_M == 1 and not dist_on and ngroups > 0:
+        if FUSED_FINALIZE and lead_M == 1 and not dist_on and ngroups > 0 and not many_served:
             fin = _fused_finish(func, agg.op_set, vals.dtype, out_dtype, min_count_, fill_value)
         p = run_set(agg.op_set, agg.skipnan) if fin is None else run_set(
             agg.op_set, agg.skipnan, finish=fin
@@ -1344,9 +1432,7 @@ def groupby_reduce(
                 )
         else:
             result = result.to(t_out_dtype)
-            result = torch.where(
-                mask, torch.tensor(fill_value, dtype=t_out_dtype, device=device), result
-            )
+            result = torch.where(mask, _fill_scalar(fill_value, t_out_dtype, device, result), result)
     else:
         fv = fill_value if fill_value is not None else xrdtypes.fill_default(func, out_dtype)
         nan_fv = isinstance(fv, float) and math.isnan(fv)
@@ -1366,9 +1452,7 @@ def groupby_reduce(
             if empty_mask is None:
                 empty_mask = counts_for_mask == 0
             result = result.to(t_out_dtype)
-            result = torch.where(
-                empty_mask, torch.tensor(fv, dtype=t_out_dtype, device=device), result
-            )
+            result = torch.where(empty_mask, _fill_scalar(fv, t_out_dtype, device, result), result)
 
     result = result.to(t_out_dtype)
     if lead_M > 1 and not lead_folded:
@@ -1393,12 +1477,18 @@ def groupby_reduce(
                 fcodes = (
                     fcodes.reshape(by_shape).permute(subset_by_inv).reshape(-1)
                 ).contiguous()
-            pidx = grouped_partials(
-                _ffi.SET_IDXMIN, fcodes.to(torch.int64), fcodes, f.ngroups
-            )
-            order = torch.argsort(pidx["idx"], stable=True)
+            if many is not None and ax_i in many.orders:
+                order, order_np = many.orders[ax_i]
+            else:
+                pidx = grouped_partials(
+                    _ffi.SET_IDXMIN, fcodes.to(torch.int64), fcodes, f.ngroups
+                )
+                order = torch.argsort(pidx["idx"], stable=True)
+                order_np = order.cpu().numpy()
+                if many is not None:
+                    many.orders[ax_i] = (order, order_np)
             result = torch.index_select(result, result.dim() - len(facs) + ax_i, order)
-            groups_list[ax_i] = np.asarray(groups_list[ax_i])[order.cpu().numpy()]
+            groups_list[ax_i] = np.asarray(groups_list[ax_i])[order_np]
     groups = tuple(groups_list)
     if return_numpy:
         out_np = result.cpu().numpy()
@@ -1418,3 +1508,112 @@ def groupby_reduce(
         if np.dtype(small_dtype) in _back:
             result = result.to(_back[np.dtype(small_dtype)])
     return (result, *groups)
+
+
+_PER_FUNC_ARGS = ("fill_value", "dtype", "min_count", "finalize_kwargs")
+
+
+def _per_func(name, value, funcs):
+    """Resolve one of the per-func arguments of groupby_reduce_many: a dict
+    keyed by func name (missing key = the argument's default, None), or one
+    value for every func. finalize_kwargs is itself a dict, so it counts as
+    keyed by func only when all its values are dicts (or None)."""
+    keyed = isinstance(value, dict)
+    if keyed and name == "finalize_kwargs":
+        keyed = len(value) > 0 and all(v is None or isinstance(v, dict) for v in value.values())
+    if not keyed:
+        return {f: value for f in funcs}
+    extra = [k for k in value if k not in funcs]
+    if extra:
+        raise ValueError(f"{name} has keys that are not in funcs: {extra}")
+    return {f: value.get(f) for f in funcs}
+
+
+def groupby_reduce_many(
+    array,
+    *by,
+    funcs,
+    expected_groups=None,
+    sort: bool = True,
+    isbin=False,
+    axis=None,
+    fill_value=None,
+    dtype=None,
+    min_count=None,
+    method: str | None = None,
+    engine: str = "hip",
+    reindex=None,
+    finalize_kwargs=None,
+    distributed_combine: bool | None = None,
+    shard_row_offset: int = 0,
+):
+    """Several grouped reductions of one array over the same labels.
+    Returns (results, *groups): results maps each name in ``funcs`` (in that
+    order) to what ``groupby_reduce(array, *by, func=name, ...)`` returns.
+
+    ``fill_value``, ``dtype``, ``min_count`` and ``finalize_kwargs`` take one
+    value for all funcs or a dict keyed by func name (see _per_func).
+
+    The labels are factorized once. When at least two names belong to
+    FUSED_MANY_FUNCS (the sum/mean/var/std/min/max/count family and its nan*
+    twins) and the call is a non-distributed 1-D reduction of real
+    f32/f64/i32/i64 values whose bins fit LDS, those names share ONE pass
+    over the rows (SET_SUMMARY); every other name, and every name of a call
+    that is not eligible, runs its usual passes. ``set_options(fused_many=
+    False)`` turns the sharing off. Results do not depend on which way a
+    name was served beyond float rounding of sum/mean/var/std.
+    """
+    global _MANY
+
+    if isinstance(funcs, str):
+        funcs = (funcs,) if funcs else ()
+    funcs = tuple(funcs)
+    if not funcs:
+        raise ValueError("funcs must name at least one reduction")
+    for f in funcs:
+        if not isinstance(f, str) or f not in REDUCTIONS:
+            raise NotImplementedError(f"reduction {f!r}")
+    if len(set(funcs)) != len(funcs):
+        dup = sorted({f for f in funcs if funcs.count(f) > 1})
+        raise ValueError(f"funcs lists a reduction more than once: {dup}")
+    per = {
+        "fill_value": _per_func("fill_value", fill_value, funcs),
+        "dtype": _per_func("dtype", dtype, funcs),
+        "min_count": _per_func("min_count", min_count, funcs),
+        "finalize_kwargs": _per_func("finalize_kwargs", finalize_kwargs, funcs),
+    }
+
+    is_complex = (
+        array.is_complex() if isinstance(array, torch.Tensor)
+        else np.asarray(array).dtype.kind == "c"
+    )
+    share = (
+        FUSED_MANY
+        and not is_complex  # complex input re-enters groupby_reduce on views
+        and sum(f in FUSED_MANY_FUNCS for f in funcs) >= 2
+    )
+    results, groups = {}, ()
+    prev = _MANY
+    _MANY = _ManyCall() if share else None
+    try:
+        state = _MANY
+        for f in funcs:
+            r, *groups = groupby_reduce(
+                array, *by, func=f, expected_groups=expected_groups, sort=sort,
+                isbin=isbin, axis=axis, method=method, engine=engine,
+                reindex=reindex, distributed_combine=distributed_combine,
+                shard_row_offset=shard_row_offset,
+                **{k: per[k][f] for k in _PER_FUNC_ARGS},
+            )
+            results[f] = r
+        if state is not None and state.partials is not None:
+            # a result that needed no fill and no cast can be a partial
+            # itself: hand out copies, so no two results share storage
+            shared = {t.data_ptr() for t in state.partials.values()
+                      if isinstance(t, torch.Tensor)}
+            for f, r in results.items():
+                if isinstance(r, torch.Tensor) and r.data_ptr() in shared:
+                    results[f] = r.clone()
+    finally:
+        _MANY = prev
+    return (results, *groups)

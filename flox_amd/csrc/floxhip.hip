@@ -66,7 +66,11 @@ enum {
   B_WELFORD = 1024,
   B_ARGROW = 2048, /* pair-payload arg-reductions: second bucket pass takes
                       the min row among rows matching the group extremum */
+  B_MOM2 = 4096,   /* pivoted single-pass second moment (FH_SET_SUMMARY); with
+                      it B_MIN and B_MAX may both be set: min keeps
+                      minmax_off, max takes max_off */
 };
+constexpr int OPS_SUMMARY = B_SUM | B_CNT | B_MIN | B_MAX | B_NANFLAG | B_MOM2;
 
 __host__ __device__ constexpr int set_bits(int op_set) {
   switch (op_set) {
@@ -84,6 +88,7 @@ __host__ __device__ constexpr int set_bits(int op_set) {
     case FH_SET_WELFORD: return B_WELFORD | B_CNT;
     case FH_SET_ARGMIN_PAIR: return B_MIN | B_CNT | B_PRESENT | B_NANFLAG | B_ARGROW;
     case FH_SET_ARGMAX_PAIR: return B_MAX | B_CNT | B_PRESENT | B_NANFLAG | B_ARGROW;
+    case FH_SET_SUMMARY: return B_SUM | B_CNT | B_MIN | B_MAX | B_NANFLAG | B_MOM2;
     default: return 0;
   }
 }
@@ -105,6 +110,9 @@ template <> struct Traits<float> {
     return __uint_as_float(r);
   }
   static __device__ __forceinline__ float pos_inf() { return __builtin_inff(); }
+  /* pivot slot of the summary set: never 0 (0 decodes to a NaN), so 0 = EMPTY */
+  static __device__ __forceinline__ Enc piv_enc(float v) { return enc(v); }
+  static __device__ __forceinline__ double piv_dec(Enc e) { return (double)dec(e); }
 };
 
 template <> struct Traits<double> {
@@ -121,6 +129,8 @@ template <> struct Traits<double> {
     return __longlong_as_double((long long)r);
   }
   static __device__ __forceinline__ double pos_inf() { return __builtin_inf(); }
+  static __device__ __forceinline__ Enc piv_enc(double v) { return enc(v); }
+  static __device__ __forceinline__ double piv_dec(Enc e) { return dec(e); }
 };
 
 template <> struct Traits<int32_t> {
@@ -133,6 +143,10 @@ template <> struct Traits<int32_t> {
   }
   static __device__ __forceinline__ int32_t dec(Enc u) { return (int32_t)(u ^ 0x80000000u); }
   static __device__ __forceinline__ int32_t pos_inf() { return INT32_MAX; }
+  /* every integer is a legal value, so the pivot is the value with bit 0 set:
+   * within 1 of a row of the group (all a pivot has to be) and never 0 = EMPTY */
+  static __device__ __forceinline__ Enc piv_enc(int32_t v) { return (uint32_t)v | 1u; }
+  static __device__ __forceinline__ double piv_dec(Enc e) { return (double)(int32_t)e; }
 };
 
 template <> struct Traits<int64_t> {
@@ -147,6 +161,8 @@ template <> struct Traits<int64_t> {
     return (int64_t)(u ^ 0x8000000000000000ull);
   }
   static __device__ __forceinline__ int64_t pos_inf() { return INT64_MAX; }
+  static __device__ __forceinline__ Enc piv_enc(int64_t v) { return (uint64_t)v | 1ull; }
+  static __device__ __forceinline__ double piv_dec(Enc e) { return (double)(int64_t)e; }
 };
 
 /* atomic add on the accumulator type (LDS or global pointer) */
@@ -161,6 +177,14 @@ __device__ __forceinline__ void enc_min(uint64_t* p, uint64_t v) {
 __device__ __forceinline__ void enc_max(uint32_t* p, uint32_t v) { atomicMax(p, v); }
 __device__ __forceinline__ void enc_max(uint64_t* p, uint64_t v) {
   atomicMax(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
+}
+/* claim an EMPTY (0) slot; returns what the slot held before */
+__device__ __forceinline__ uint32_t enc_claim(uint32_t* p, uint32_t v) {
+  return atomicCAS(p, 0u, v);
+}
+__device__ __forceinline__ uint64_t enc_claim(uint64_t* p, uint64_t v) {
+  return (uint64_t)atomicCAS(reinterpret_cast<unsigned long long*>(p), 0ull,
+                             (unsigned long long)v);
 }
 __device__ __forceinline__ void idx_min(int64_t* p, int64_t v) {
   atomicMin(reinterpret_cast<long long*>(p), (long long)v);
@@ -195,6 +219,10 @@ template <typename T, int N> struct alignas(sizeof(T) * N) Vec { T v[N]; };
 struct BinLayout {
   int64_t sum_off, cnt_off, present_off, minmax_off, nanflag_off, sumx_off;
   int64_t bytes;  /* per block-copy of the bins */
+  /* B_MOM2 only, carved after every older section: max (minmax_off is then
+   * the min), the pivot x0, s1 and s2 (in the slab: the block's mean as
+   * x0 + s1/n, and its M2) */
+  int64_t max_off, s1_off, s2_off, pivot_off;
 };
 
 template <typename V>
@@ -212,6 +240,13 @@ __host__ __device__ BinLayout bin_layout(int bits, int64_t ngroups, int64_t cnt_
   L.minmax_off = (bits & (B_MIN | B_MAX)) ? carve(sizeof(typename Traits<V>::Enc)) : -1;
   L.nanflag_off = (bits & B_NANFLAG) ? carve(4) : -1;
   L.sumx_off = (bits & B_WELFORD) ? carve(8) : -1;
+  L.max_off = L.s1_off = L.s2_off = L.pivot_off = -1;
+  if (bits & B_MOM2) {
+    L.max_off = carve(sizeof(typename Traits<V>::Enc));
+    L.s1_off = carve(8);
+    L.s2_off = carve(8);
+    L.pivot_off = carve(sizeof(typename Traits<V>::Enc));
+  }
   L.bytes = off;
   return L;
 }
@@ -262,6 +297,8 @@ __launch_bounds__(BLOCK_LDS) __global__ void k_reduce_lds(
   using Enc = typename TR::Enc;
   constexpr int VEC = TR::VEC;
   constexpr bool IS_PROD = (OPS & B_PROD) != 0;
+  constexpr bool MOM2 = (OPS & B_MOM2) != 0;
+  static_assert(!MOM2 || OPS == OPS_SUMMARY, "B_MOM2 exists in the summary set only");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   SumT* s_sum = (OPS & (B_SUM | B_SSD | B_PROD | B_IDXMIN | B_IDXMAX)) ? (SumT*)(smem + lay.sum_off) : nullptr;
@@ -269,6 +306,11 @@ __launch_bounds__(BLOCK_LDS) __global__ void k_reduce_lds(
   uint32_t* s_present = (OPS & B_PRESENT) ? (uint32_t*)(smem + lay.present_off) : nullptr;
   Enc* s_mm = (OPS & (B_MIN | B_MAX)) ? (Enc*)(smem + lay.minmax_off) : nullptr;
   uint32_t* s_nanflag = (OPS & B_NANFLAG) ? (uint32_t*)(smem + lay.nanflag_off) : nullptr;
+  /* summary set: s_mm is the min, the max has its own section */
+  Enc* s_mx = MOM2 ? (Enc*)(smem + lay.max_off) : s_mm;
+  double* s_s1 = MOM2 ? (double*)(smem + lay.s1_off) : nullptr;
+  double* s_s2 = MOM2 ? (double*)(smem + lay.s2_off) : nullptr;
+  Enc* s_piv = MOM2 ? (Enc*)(smem + lay.pivot_off) : nullptr;
 
   const int tid = threadIdx.x;
   for (int64_t g = tid; g < ngroups; g += blockDim.x) {
@@ -279,8 +321,13 @@ __launch_bounds__(BLOCK_LDS) __global__ void k_reduce_lds(
     if (OPS & B_CNT) s_cnt[g] = 0u;
     if (OPS & B_PRESENT) s_present[g] = 0u;
     if (OPS & B_MIN) s_mm[g] = (Enc)~(Enc)0;
-    if (OPS & B_MAX) s_mm[g] = (Enc)0;
+    if (OPS & B_MAX) s_mx[g] = (Enc)0;
     if (OPS & B_NANFLAG) s_nanflag[g] = 0u;
+    if constexpr (MOM2) {
+      s_s1[g] = 0.0;
+      s_s2[g] = 0.0;
+      s_piv[g] = (Enc)0; /* EMPTY */
+    }
   }
   __syncthreads();
 
@@ -299,6 +346,13 @@ __launch_bounds__(BLOCK_LDS) __global__ void k_reduce_lds(
     const uint32_t rcode = (uint32_t)code;
     const bool vnan = TR::isnan_(v);
     if (OPS & B_PRESENT) s_present[code] = 1u;  /* benign write race: all store 1 */
+    if constexpr (MOM2) {
+      /* a NaN row leaves its mark and nothing else, whatever skipnan says */
+      if (vnan) {
+        s_nanflag[code] = 1u;
+        return rcode;
+      }
+    }
     if (vnan && skipnan) return rcode;
     if (OPS & B_SUM) acc_add(&s_sum[code], (Acc)v);
     if (IS_PROD) acc_mul(&s_sum[code], (Acc)v);
@@ -328,8 +382,22 @@ __launch_bounds__(BLOCK_LDS) __global__ void k_reduce_lds(
         if (OPS & B_NANFLAG) s_nanflag[code] = 1u;
       } else {
         if (OPS & B_MIN) enc_min(&s_mm[code], TR::enc(v));
-        if (OPS & B_MAX) enc_max(&s_mm[code], TR::enc(v));
+        if (OPS & B_MAX) enc_max(&s_mx[code], TR::enc(v));
       }
+    }
+    if constexpr (MOM2) {
+      /* deviations about the block's pivot for this group: the first value
+       * to claim the slot. Steady state is one plain LDS read; a stale EMPTY
+       * only costs a CAS that returns the pivot already there. */
+      Enc pe = s_piv[code];
+      if (pe == (Enc)0) {
+        const Enc mine = TR::piv_enc(v);
+        const Enc old = enc_claim(&s_piv[code], mine);
+        pe = old != (Enc)0 ? old : mine;
+      }
+      const double d = (double)v - TR::piv_dec(pe);
+      atomicAdd(&s_s1[code], d);
+      atomicAdd(&s_s2[code], d * d);
     }
     return rcode;
   };
@@ -406,6 +474,24 @@ __launch_bounds__(BLOCK_LDS) __global__ void k_reduce_lds(
     if (OPS & B_PRESENT) ((uint32_t*)(my + lay.present_off))[g] = s_present[g];
     if (OPS & (B_MIN | B_MAX)) ((Enc*)(my + lay.minmax_off))[g] = s_mm[g];
     if (OPS & B_NANFLAG) ((uint32_t*)(my + lay.nanflag_off))[g] = s_nanflag[g];
+    if constexpr (MOM2) {
+      ((Enc*)(my + lay.max_off))[g] = s_mx[g];
+      /* the block's (n, mean, M2) triple; n travels in the count section and
+       * the mean in two parts, pivot x0 and offset s1/n: summed into one
+       * double it would round at ulp(x0), and the merge is first-order in
+       * the difference of two means */
+      const uint32_t nb = s_cnt[g];
+      double off_b = 0.0, m2_b = 0.0;
+      if (nb) {
+        const double s1 = s_s1[g], s2 = s_s2[g], dn = (double)nb;
+        off_b = s1 / dn;
+        m2_b = s2 - s1 * s1 / dn;
+        if (m2_b < 0.0) m2_b = 0.0; /* rounding only: M2 >= 0 by Cauchy-Schwarz */
+      }
+      ((Enc*)(my + lay.pivot_off))[g] = s_piv[g];
+      ((double*)(my + lay.s1_off))[g] = off_b;
+      ((double*)(my + lay.s2_off))[g] = m2_b;
+    }
   }
 }
 
@@ -527,11 +613,33 @@ __device__ __forceinline__ void store_finished(const FinishArgs& fa, int64_t g,
   }
 }
 
+/* Chan's pairwise merge of two (n, mean, M2) partials into a; an empty side
+ * is skipped, so no 0/0 enters. Unlike the closed form k_combine uses for the
+ * column path it never subtracts squared sums, so it stays accurate when
+ * mean^2 >> var. A mean is piv + off, piv a value of the group: the pivots
+ * subtract exactly where the data is clustered (the hard case) and the
+ * offsets are small, so d keeps the precision a single rounded mean loses.
+ * The merged mean stays relative to a's pivot. */
+__device__ __forceinline__ void chan_merge(double na, double& piv_a, double& off_a,
+                                           double& m2_a, double nb, double piv_b,
+                                           double off_b, double m2_b) {
+  if (nb == 0.0) return;
+  if (na == 0.0) {
+    piv_a = piv_b;
+    off_a = off_b;
+    m2_a = m2_b;
+    return;
+  }
+  const double nt = na + nb, d = (piv_b - piv_a) + (off_b - off_a);
+  off_a += d * (nb / nt);
+  m2_a += m2_b + d * d * (na * nb / nt);
+}
+
 template <typename V, int OPS, int FIN>
 __launch_bounds__(CT_X * CT_Y) __global__ void k_combine_tree(
     const char* __restrict__ slab, int nblocks, int64_t ngroups, BinLayout lay,
     void* out_sum, int64_t* out_count, uint32_t* out_present, void* out_min,
-    void* out_max, uint32_t* out_nanflag, FinishArgs fa) {
+    void* out_max, uint32_t* out_nanflag, double* out_ssd, FinishArgs fa) {
   using TR = Traits<V>;
   using Acc = typename TR::Acc;
   using SumT = typename std::conditional<
@@ -542,6 +650,7 @@ __launch_bounds__(CT_X * CT_Y) __global__ void k_combine_tree(
   constexpr bool HAS_S = (OPS & (B_SUM | B_SSD | B_PROD | B_IDXMIN | B_IDXMAX)) != 0;
   constexpr bool HAS_MM = (OPS & (B_MIN | B_MAX)) != 0;
   constexpr bool HAS_FLAGS = (OPS & (B_PRESENT | B_NANFLAG)) != 0;
+  constexpr bool MOM2 = (OPS & B_MOM2) != 0;
   static_assert(FIN == FIN_NONE || FIN == finish_of(OPS), "finish mode/op set mismatch");
   constexpr int NT = CT_X * CT_Y;
 
@@ -549,6 +658,12 @@ __launch_bounds__(CT_X * CT_Y) __global__ void k_combine_tree(
   __shared__ int64_t sh_c[(OPS & B_CNT) ? NT : 1];
   __shared__ Enc sh_mm[HAS_MM ? NT : 1];
   __shared__ uint32_t sh_f[HAS_FLAGS ? NT : 1]; /* bit 0 present, bit 1 nanflag */
+  /* summary set: mm is the min and mx the max; (c, piv + off, m2) is the
+   * triple */
+  __shared__ Enc sh_mx[MOM2 ? NT : 1];
+  __shared__ double sh_piv[MOM2 ? NT : 1];
+  __shared__ double sh_off[MOM2 ? NT : 1];
+  __shared__ double sh_m2[MOM2 ? NT : 1];
 
   const int tx = threadIdx.x, ty = threadIdx.y;
   const int t = ty * CT_X + tx;
@@ -561,10 +676,21 @@ __launch_bounds__(CT_X * CT_Y) __global__ void k_combine_tree(
   int64_t c = 0;
   uint32_t f = 0;
   Enc mm = (OPS & B_MIN) ? (Enc)~(Enc)0 : (Enc)0;
+  Enc mx = (Enc)0;
+  double piv = 0.0, off = 0.0, m2 = 0.0;
   if (live) {
 #pragma unroll 4
     for (int b = ty; b < nblocks; b += CT_Y) {
       const char* blk = slab + (int64_t)b * lay.bytes;
+      if constexpr (MOM2) { /* before c takes this block's count */
+        chan_merge((double)c, piv, off, m2,
+                   (double)((const uint32_t*)(blk + lay.cnt_off))[g],
+                   TR::piv_dec(((const Enc*)(blk + lay.pivot_off))[g]),
+                   ((const double*)(blk + lay.s1_off))[g],
+                   ((const double*)(blk + lay.s2_off))[g]);
+        const Enc e = ((const Enc*)(blk + lay.max_off))[g];
+        mx = e > mx ? e : mx;
+      }
       if (HAS_S) {
         const SumT x = ((const SumT*)(blk + lay.sum_off))[g];
         if (OPS & (B_SUM | B_SSD)) s += x;
@@ -578,9 +704,15 @@ __launch_bounds__(CT_X * CT_Y) __global__ void k_combine_tree(
       if (HAS_MM) {
         const Enc e = ((const Enc*)(blk + lay.minmax_off))[g];
         if (OPS & B_MIN) mm = e < mm ? e : mm;
-        if (OPS & B_MAX) mm = e > mm ? e : mm;
+        if ((OPS & B_MAX) && !MOM2) mm = e > mm ? e : mm;
       }
     }
+  }
+  if constexpr (MOM2) {
+    sh_mx[t] = mx;
+    sh_piv[t] = piv;
+    sh_off[t] = off;
+    sh_m2[t] = m2;
   }
   if (HAS_S) sh_s[t] = s;
   if (OPS & B_CNT) sh_c[t] = c;
@@ -592,6 +724,15 @@ __launch_bounds__(CT_X * CT_Y) __global__ void k_combine_tree(
   for (int h = CT_Y / 2; h > 0; h >>= 1) {
     if (ty < h) {
       const int o = t + h * CT_X;
+      if constexpr (MOM2) { /* before c takes row o's count */
+        chan_merge((double)c, piv, off, m2, (double)sh_c[o], sh_piv[o], sh_off[o], sh_m2[o]);
+        sh_piv[t] = piv;
+        sh_off[t] = off;
+        sh_m2[t] = m2;
+        const Enc e = sh_mx[o];
+        mx = e > mx ? e : mx;
+        sh_mx[t] = mx;
+      }
       if (HAS_S) {
         const SumT x = sh_s[o];
         if (OPS & (B_SUM | B_SSD)) s += x;
@@ -605,7 +746,7 @@ __launch_bounds__(CT_X * CT_Y) __global__ void k_combine_tree(
       if (HAS_MM) {
         const Enc e = sh_mm[o];
         if (OPS & B_MIN) mm = e < mm ? e : mm;
-        if (OPS & B_MAX) mm = e > mm ? e : mm;
+        if ((OPS & B_MAX) && !MOM2) mm = e > mm ? e : mm;
         sh_mm[t] = mm;
       }
     }
@@ -625,8 +766,12 @@ __launch_bounds__(CT_X * CT_Y) __global__ void k_combine_tree(
     if (OPS & B_CNT) out_count[g] = c;
     if (OPS & B_PRESENT) out_present[g] = p;
     if (OPS & B_MIN) ((V*)out_min)[g] = present ? TR::dec(mm) : TR::pos_inf();
-    if (OPS & B_MAX) ((V*)out_max)[g] = present ? TR::dec(mm) : (V)-TR::pos_inf();
+    if (OPS & B_MAX) ((V*)out_max)[g] = present ? TR::dec(MOM2 ? mx : mm) : (V)-TR::pos_inf();
     if (OPS & B_NANFLAG) out_nanflag[g] = nf;
+    if constexpr (MOM2) {
+      out_present[g] = (c != 0 || nf != 0) ? 1u : 0u; /* any row seen */
+      out_ssd[g] = m2;
+    }
   }
 }
 
@@ -2441,6 +2586,12 @@ int launch_typed(fh_call* c) {
       return 14;
   }
 
+  if constexpr ((OPS & B_MOM2) != 0) {
+    /* the summary set exists on the LDS-binned path only */
+    if (lay.bytes > LDS_MAX || (c->flags & FH_FORCE_ATOMIC)) return 15;
+    if (!c->out_ssd) return 16;
+  }
+
   if constexpr (U16) {
     /* compact codes exist for the LDS-binned kernel only */
     if ((OPS & B_ARGROW) || c->labels2 || c->emit_codes ||
@@ -2501,12 +2652,14 @@ int launch_typed(fh_call* c) {
     hipLaunchKernelGGL(comb, dim3(cb), dim3(CT_X, CT_Y), 0, stream,
                        (const char*)c->scratch, nblocks, c->ngroups, lay,
                        c->out_sum, c->out_count, c->out_present, c->out_min,
-                       c->out_max, c->out_nanflag, fa);
+                       c->out_max, c->out_nanflag, (double*)c->out_ssd, fa);
     FH_CHECK(hipGetLastError());
     c->path_used = 1;
     return 0;
   }
-  if constexpr (U16)
+  if constexpr ((OPS & B_MOM2) != 0)
+    return 15; /* not reached: refused above */
+  else if constexpr (U16)
     return 12; /* not reached: the guard above admits LDS-sized bins only */
   else
     return launch_beyond_lds<V, L, OPS>(c);
@@ -2532,6 +2685,7 @@ int dispatch_ops(fh_call* c) {
       return launch_typed<V, L, B_IDXMIN | B_CNT | B_PRESENT>(c);
     case B_IDXMAX | B_CNT | B_PRESENT:
       return launch_typed<V, L, B_IDXMAX | B_CNT | B_PRESENT>(c);
+    case OPS_SUMMARY: return launch_typed<V, L, OPS_SUMMARY>(c);
     case B_MIN | B_CNT | B_PRESENT | B_NANFLAG | B_ARGROW:
       if constexpr (std::is_same<L, uint16_t>::value)
         return 12; /* partition path only: no compact-code form */
@@ -2791,6 +2945,10 @@ int64_t fh_scratch_bytes(const fh_call* c) {
     case FH_I32: per_block = bin_layout<int32_t>(bits, c->ngroups, 4).bytes; break;
     default: return -1;
   }
+  if (bits & B_MOM2) {
+    /* LDS-binned path or nothing (error 15): never a partition plan */
+    if (c->m > 0 || per_block > LDS_MAX) return 0;
+  }
   if (c->m > 0) {
     if (c->chunk_offsets) return 0; /* group-aligned chunks write directly */
     /* column path: per-chunk slab when the row range is split */
@@ -2858,6 +3016,7 @@ int fh_grouped_reduce_cols(fh_call* c) {
    * Outputs are (ngroups, m) group-major. */
   if (!c || !c->values || !c->labels || !c->perm) return 6;
   if (c->finish) return 14;
+  if (c->op_set == FH_SET_SUMMARY) return 15;
   if (c->op_set == FH_SET_SSD && !c->means) return 8;
   switch (c->vdtype) {
     case FH_F32: return dispatch_cols_ops<float>(c);
@@ -2905,11 +3064,13 @@ const char* fh_error_string(int code) {
     case 12: return "uint16 code labels are valid on the LDS-binned path only (single code stream, bins within LDS; see fh_query_path)";
     case 13: return "emit_codes needs the LDS-binned path and ngroups < 65535";
     case 14: return "finish mode needs the LDS-binned path, the op set it finishes (mean: SUM_COUNT, sum: SUM_COUNT_PRESENT, count: COUNT) and an f32/f64/i64 result buffer (see fh_query_path)";
+    case 15: return "FH_SET_SUMMARY is served by the LDS-binned path only (bins within LDS, no FH_FORCE_ATOMIC, not the column path; see fh_query_path)";
+    case 16: return "FH_SET_SUMMARY requires out_ssd";
     default: return code >= 1000 ? hipGetErrorString((hipError_t)(code - 1000)) : "unknown error";
   }
 }
 
 int fh_version(void) { return 1; }
-int fh_abi_revision(void) { return 3; }
+int fh_abi_revision(void) { return 4; }
 
 }  /* extern "C" */

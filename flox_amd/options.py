@@ -15,6 +15,9 @@ Supported options:
   fused_finalize: False makes mean/sum/count return to per-group partials
       finished by torch ops; on (the default) the combine kernel writes the
       finished result where the LDS-binned path serves the call (core.py).
+  fused_many: False makes groupby_reduce_many run every func through its own
+      groupby_reduce passes; on (the default) the sum/mean/var/std/min/max/
+      count family shares one SET_SUMMARY pass on eligible calls (core.py).
 """
 
 from __future__ import annotations
@@ -29,6 +32,7 @@ OPTIONS = {
     "label_cache_entries": None,
     "label_cache_bytes": None,
     "fused_finalize": None,           # None = on
+    "fused_many": None,               # None = on
 }
 
 _CACHE_FIELDS = {
@@ -57,6 +61,11 @@ def _apply(name, value):
         if value is not None:
             core.FUSED_FINALIZE = bool(value)
         return ("fused_finalize", old)
+    if name == "fused_many":
+        old = core.FUSED_MANY
+        if value is not None:
+            core.FUSED_MANY = bool(value)
+        return ("fused_many", old)
     if name == "sparse_combine_ngroups":
         old = distributed.SPARSE_NGROUPS
         if value is not None:
@@ -81,6 +90,8 @@ def _restore(name, old):
         core.PACKED_ARG_THRESHOLD = old
     elif name == "fused_finalize":
         core.FUSED_FINALIZE = old
+    elif name == "fused_many":
+        core.FUSED_MANY = old
     elif name == "sparse_combine_ngroups":
         distributed.SPARSE_NGROUPS = old
     elif name == "sparse_combine_fraction":

@@ -88,6 +88,26 @@ enum fh_opset {
    * out_min/out_max = the decoded extremum, plus count/present/nanflag. */
   FH_SET_ARGMIN_PAIR = 12,
   FH_SET_ARGMAX_PAIR = 13,
+  /* every partial the sum/mean/var/std/min/max/count family (and its nan*
+   * twins) needs, from ONE pass on the LDS-binned path. NaN rows contribute
+   * nothing to any member but nanflag (FH_SKIPNAN is implied), so the
+   * non-skipping functions are derived by the caller: NaN where nanflag is
+   * set. Outputs: out_sum (f64 / i64, as FH_SET_SUM_COUNT), out_count (non-NaN
+   * rows), out_min / out_max (value dtype, +inf/-inf or INT_MAX/MIN where
+   * count == 0), out_nanflag, out_present (count > 0 || nanflag, i.e. "any
+   * row seen") and out_ssd: f64 sum of squared deviations about the group
+   * mean. The second moment needs no input from the caller: each workgroup
+   * keeps, per group, a pivot x0 (a value it saw for the group) with
+   * s1 = sum(x - x0) and s2 = sum((x - x0)^2) in f64, flushes the triple
+   * (n_b, mean_b = x0 + s1/n_b, M2_b = s2 - s1^2/n_b), the mean kept as its
+   * two parts so that differences of means stay exact, and the combine folds
+   * the triples in a fixed order with Chan's pairwise merge
+   * M2 = M2_a + M2_b + d^2 n_a n_b / (n_a + n_b), d = mean_b - mean_a.
+   * Served by the LDS-binned path only (fh_query_path() == 1): any other
+   * dispatch of fh_grouped_reduce returns error 15 without launching, and
+   * fh_grouped_reduce_cols rejects the set. No finish mode applies
+   * (error 14). */
+  FH_SET_SUMMARY = 14,
 };
 
 /* flags */
@@ -187,6 +207,8 @@ typedef struct fh_call {
   int64_t min_count;
   int has_fill;
   double fill;
+  /* FH_SET_SUMMARY: f64[ngroups] sum of squared deviations about the mean */
+  void* out_ssd;
 } fh_call;
 
 /* scratch requirement for this call (0 when the global-atomic path is used) */
@@ -218,7 +240,8 @@ int fh_pack_argkeys(const void* values, int vdtype, int64_t n,
 const char* fh_error_string(int code);
 int fh_version(void);
 /* append-only revisions of fh_call within one fh_version: 2 added
- * emit_codes, FH_L_U16 and fh_query_path; 3 added the finish fields. A caller built against revision R
+ * emit_codes, FH_L_U16 and fh_query_path; 3 added the finish fields; 4 added
+ * FH_SET_SUMMARY and out_ssd. A caller built against revision R
  * needs a library with fh_abi_revision() >= R. */
 int fh_abi_revision(void);
 
