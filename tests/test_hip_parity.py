@@ -673,6 +673,25 @@ def test_nosort_subset_and_mode():
     np.testing.assert_array_equal(np.asarray(got), want)
 
 
+@pytest.mark.parametrize("func,fk", [("median", None), ("nanquantile", {"q": [0.25, 0.75]})])
+def test_nosort_axis_subset_quantile_order(func, fk):
+    """sort=False group order under an axis subset is first appearance in the
+    ORIGINAL by layout: row 0 reads 2, 1, 0 while column 0 (what leads once
+    the reduced axis is moved last) reads 2, 0, 1."""
+    by = np.array([[2, 1, 0, 2, 1, 0],
+                   [0, 2, 1, 0, 2, 1],
+                   [1, 0, 2, 1, 0, 2],
+                   [2, 1, 0, 2, 1, 0]])
+    arr = np.random.default_rng(5).standard_normal((4, 6))
+    kw = dict(func=func, axis=0, sort=False, finalize_kwargs=fk)
+    want, wg = oracle_reduce(arr, by, **kw)
+    got, gg = flox_amd.groupby_reduce(arr, by, **kw)
+    np.testing.assert_array_equal(np.asarray(gg), wg)
+    np.testing.assert_array_equal(wg, [2, 1, 0])
+    assert got.dtype == want.dtype and got.shape == want.shape
+    np.testing.assert_allclose(got, want, equal_nan=True, rtol=1e-12, atol=1e-12)
+
+
 @pytest.mark.parametrize("dtype", ["float32", "float64", "int64"])
 @pytest.mark.parametrize("skipnan", [False, True])
 def test_distributed_mode_world1(dtype, skipnan):
