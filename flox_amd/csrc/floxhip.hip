@@ -44,6 +44,13 @@
     if (_e != hipSuccess) return (int)_e + 1000; \
   } while (0)
 
+/* propagate a nonzero return code of a host stage */
+#define FH_TRY(x)           \
+  do {                      \
+    int _rc = (x);          \
+    if (_rc) return _rc;    \
+  } while (0)
+
 namespace {
 
 constexpr int BLOCK_LDS = 1024;   /* 16 waves/CU at 1 block/CU */
@@ -1175,6 +1182,10 @@ constexpr int PART_BLOCK = 512;
  * slots double as the staging cursors. */
 constexpr int PART_NW = PART_BLOCK / 64;
 
+/* staging tile of both scatter passes, in pairs: ~76 KB of LDS, 2 blocks/CU */
+template <typename V>
+constexpr int PART_TILE = sizeof(V) == 4 ? 6144 : 3072;
+
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
@@ -1184,8 +1195,7 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
   return v;
 }
 
-template <typename V, typename L, bool CROW = false,
-          int T = (sizeof(V) == 4 ? 6144 : 3072)>
+template <typename V, typename L, bool CROW = false, int T = PART_TILE<V>>
 __launch_bounds__(PART_BLOCK) __global__ void k_part_scatter(
     const V* __restrict__ values, const L* __restrict__ labels,
     const L* __restrict__ labels2, int64_t n, int64_t ngroups, int64_t g0,
@@ -1332,8 +1342,7 @@ __launch_bounds__(PART_BLOCK) __global__ void k_part_scatter(
  * as k_part_scatter, with a fixed 64-entry histogram. */
 constexpr int PART_SUB = 64;
 
-template <typename V, bool CROW = false,
-          int T = (sizeof(V) == 4 ? 6144 : 3072)>
+template <typename V, bool CROW = false, int T = PART_TILE<V>>
 __launch_bounds__(PART_BLOCK) __global__ void k_part_scatter2(
     const PairT<V>* __restrict__ in, const uint32_t* __restrict__ baseA,
     uint32_t capA /* 0: baseA[sb]..baseA[sb+1]; else sb*capA..baseA[sb] */,
@@ -1449,138 +1458,6 @@ __launch_bounds__(PART_BLOCK) __global__ void k_part_scatter2(
     }
     __syncthreads();
     for (int i = tid; i < (int)total; i += PART_BLOCK) out[s_dest[i]] = s_stage[i];
-    __syncthreads();
-  }
-}
-
-/* one-level DIRECT scatter: every fine bucket (up to 4096) is a pass-A
- * target, so the second scatter pass disappears entirely — streamed bytes
- * drop from ~44 B/row (12r+8w, 8r+8w, 8r) to ~28 B/row (12r+8w, 8r).
- * There is no LDS staging: a register-blocked tile (RPT rows per thread)
- * is histogrammed in LDS, each nonempty bucket reserves its span with ONE
- * returning global atomic, and rows store their pair directly to the
- * reserved slot. Stores are short per-bucket runs (~T/B rows ≈ 100 B at
- * 1e7 groups): partial 128-B lines merge in the XCD L2 first (one
- * workgroup's run lands in one L2) and the remainder merges in the
- * 256 MiB memory-side Infinity Cache, whose capacity easily holds every
- * bucket's write frontier (B × ~2 lines ≈ 1 MB) — so the true HBM write
- * traffic stays ≈8 B/row (verify via WRITE_SIZE ratios).
- * Without the 73 KB staging, LDS is just the 16 KB histogram and the
- * kernel runs 3 workgroups/CU instead of 2 — more latency cover for the
- * scatter's pointer-chasing stores. */
-constexpr int PBD = 512;
-
-template <typename V, typename L, bool CROW = false>
-__launch_bounds__(PBD, 6) __global__ void k_part_scatter_direct(
-    const V* __restrict__ values, const L* __restrict__ labels,
-    const L* __restrict__ labels2, int64_t n, int64_t ngroups, int64_t g0,
-    int64_t g1, int shift, int B, uint32_t* __restrict__ cursors,
-    uint32_t cap /* 0 = exact bases preloaded in cursors */,
-    uint32_t* __restrict__ overflow, PairT<V>* __restrict__ pairs,
-    int64_t row_base = 0) {
-  constexpr int RPT = sizeof(V) == 4 ? 24 : 12;
-  constexpr int T = PBD * RPT; /* 12288 rows (4-B V) / 6144 (8-B V) */
-  extern __shared__ __attribute__((aligned(16))) char smem_pd[];
-  uint32_t* s_hist = (uint32_t*)smem_pd; /* [B] counts -> running cursors */
-  const bool twolab = labels2 != nullptr;
-  const int tid = threadIdx.x;
-  const uint32_t lmask = (1u << shift) - 1u;
-  constexpr uint32_t INV = 0xFFFFFFFFu;
-
-  for (int64_t tile = (int64_t)blockIdx.x * T; tile < n;
-       tile += (int64_t)gridDim.x * T) {
-    const int nt = (int)((n - tile < T) ? (n - tile) : T);
-    for (int b = tid; b < B; b += PBD) s_hist[b] = 0u;
-    __syncthreads();
-
-    V rv[RPT];
-    uint32_t rcode[RPT]; /* full code (bucket<<shift | lc), < 2^25; INV = drop */
-    const int base = tid * RPT;
-    if (base + RPT <= nt) {
-      /* per-thread CONTIGUOUS rows -> 16-B vector loads */
-      constexpr int VW = 16 / (int)sizeof(V);
-#pragma unroll
-      for (int k = 0; k < RPT; k += VW) {
-        const Vec<V, VW> vv =
-            *reinterpret_cast<const Vec<V, VW>*>(values + tile + base + k);
-#pragma unroll
-        for (int j = 0; j < VW; ++j) rv[k + j] = vv.v[j];
-      }
-      if (sizeof(L) == 8) {
-#pragma unroll
-        for (int k = 0; k < RPT; k += 2) {
-          const Vec<L, 2> lv =
-              *reinterpret_cast<const Vec<L, 2>*>(labels + tile + base + k);
-          const int64_t i = tile + base + k;
-          const int64_t c0 = code_of((int64_t)lv.v[0],
-                                     twolab ? (int64_t)labels2[i] : 0, twolab,
-                                     g0, g1, ngroups);
-          const int64_t c1 = code_of((int64_t)lv.v[1],
-                                     twolab ? (int64_t)labels2[i + 1] : 0,
-                                     twolab, g0, g1, ngroups);
-          rcode[k] = c0 >= 0 ? (uint32_t)c0 : INV;
-          rcode[k + 1] = c1 >= 0 ? (uint32_t)c1 : INV;
-          if (c0 >= 0) atomicAdd(&s_hist[rcode[k] >> shift], 1u);
-          if (c1 >= 0) atomicAdd(&s_hist[rcode[k + 1] >> shift], 1u);
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < RPT; ++k) {
-          const int64_t i = tile + base + k;
-          const int64_t c0 = code_of((int64_t)labels[i],
-                                     twolab ? (int64_t)labels2[i] : 0, twolab,
-                                     g0, g1, ngroups);
-          rcode[k] = c0 >= 0 ? (uint32_t)c0 : INV;
-          if (c0 >= 0) atomicAdd(&s_hist[rcode[k] >> shift], 1u);
-        }
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < RPT; ++k) {
-        const int idx = base + k;
-        rcode[k] = INV;
-        if (idx < nt) {
-          const int64_t i = tile + idx;
-          const int64_t c0 = code_of((int64_t)labels[i],
-                                     twolab ? (int64_t)labels2[i] : 0, twolab,
-                                     g0, g1, ngroups);
-          if (c0 >= 0) {
-            rv[k] = values[i];
-            rcode[k] = (uint32_t)c0;
-            atomicAdd(&s_hist[rcode[k] >> shift], 1u);
-          }
-        }
-      }
-    }
-    __syncthreads();
-    /* one returning global atomic per nonempty bucket reserves the tile's
-     * span; s_hist[b] becomes the running intra-tile cursor */
-    for (int b = tid; b < B; b += PBD) {
-      const uint32_t cnt = s_hist[b];
-      if (cnt) {
-        uint32_t gb = atomicAdd(&cursors[b], cnt);
-        if (cap && gb + cnt > (uint32_t)(b + 1) * cap) {
-          /* optimistic region overflow: flag it and keep writes in-bounds
-           * (results are discarded and recomputed by the exact path) */
-          *overflow = 1u;
-          gb = (uint32_t)b * cap;
-        }
-        s_hist[b] = gb;
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < RPT; ++k) {
-      if (rcode[k] != INV) {
-        const uint32_t pos = atomicAdd(&s_hist[rcode[k] >> shift], 1u);
-        PairT<V> pr{};
-        pr.v = rv[k];
-        pr.lc = rcode[k] & lmask;
-        if constexpr (CROW && sizeof(PairT<V>) == 16)
-          pr.pad = (uint32_t)(tile + base + k + row_base);
-        pairs[pos] = pr;
-      }
-    }
     __syncthreads();
   }
 }
@@ -1924,71 +1801,85 @@ __launch_bounds__(BLOCK_LDS) __global__ void k_reduce_bucket_argrow(
   }
 }
 
-/* ---- partition-path host plumbing ---------------------------------------- */
+/* ---- host launch helpers ------------------------------------------------- */
+
+/* blocks of `per` items covering n */
+inline int grid_for(int64_t n, int64_t per = 256) { return (int)((n + per - 1) / per); }
+
+/* the same, but at least one block and at most `cap` (grid-stride kernels) */
+inline int capped_grid(int64_t n, int64_t per, int cap) {
+  const int64_t wb = (n + per - 1) / per;
+  return (int)(wb < cap ? (wb > 0 ? wb : 1) : cap);
+}
+
+/* p[0..n) = v, for identities memset cannot write */
+inline hipError_t fill_bins(void* p, int64_t n, int64_t v, hipStream_t stream) {
+  hipLaunchKernelGGL(k_fill_i64, dim3(grid_for(n)), dim3(256), 0, stream,
+                     (int64_t*)p, n, v);
+  return hipGetLastError();
+}
+inline hipError_t fill_bins(void* p, int64_t n, double v, hipStream_t stream) {
+  hipLaunchKernelGGL(k_fill_f64, dim3(grid_for(n)), dim3(256), 0, stream,
+                     (double*)p, n, v);
+  return hipGetLastError();
+}
+
+/* where one copy of the bins lives: the call's output arrays (8-byte counts)
+ * or one row chunk's slab sections (4-byte counts) */
+struct BinPtrs {
+  void *sum, *cnt, *present, *min, *max, *nanflag, *sumx;
+  int cnt_bytes;
+};
+
+inline BinPtrs out_bins(const fh_call* c) {
+  /* B_WELFORD's sum-of-x rides the out_min slot */
+  return {c->out_sum, c->out_count, c->out_present, c->out_min,
+          c->out_max, c->out_nanflag, c->out_min, 8};
+}
+
+inline BinPtrs slab_bins(char* s, const BinLayout& lay) {
+  /* sections a set lacks (offset -1) are never touched; min and max share
+   * minmax_off (no slab set carries both) */
+  return {s + lay.sum_off, s + lay.cnt_off, s + lay.present_off,
+          s + lay.minmax_off, s + lay.minmax_off, s + lay.nanflag_off,
+          s + lay.sumx_off, 4};
+}
+
+/* identity-fill every section of OPS: min bins 0xFF.., max bins 0x00.. (the
+ * order-preserving encoding), products 1, row-index bins INT64_MAX (IDXMIN,
+ * and ARGROW: min-row on both argmin and argmax, first occurrence) or -1
+ * (IDXMAX), everything else 0 */
 template <typename V, int OPS>
-int init_outs(fh_call* c, int64_t nbins, hipStream_t stream) {
+int init_bins(const BinPtrs& b, int64_t nbins, hipStream_t stream) {
   using TR = Traits<V>;
-  if (OPS & (B_SUM | B_SSD)) FH_CHECK(hipMemsetAsync(c->out_sum, 0, nbins * 8, stream));
-  if (OPS & (B_IDXMIN | B_IDXMAX)) {
-    int fb = (int)((nbins + 255) / 256);
-    hipLaunchKernelGGL(k_fill_i64, dim3(fb), dim3(256), 0, stream,
-                       (int64_t*)c->out_sum, nbins,
-                       (OPS & B_IDXMIN) ? INT64_MAX : (int64_t)-1);
-    FH_CHECK(hipGetLastError());
-  }
-  if (OPS & B_ARGROW) {
-    /* row-index bins (out_sum as int64): min-row on both argmin and argmax
-     * (first occurrence), sentinel INT64_MAX for empty */
-    int fb = (int)((nbins + 255) / 256);
-    hipLaunchKernelGGL(k_fill_i64, dim3(fb), dim3(256), 0, stream,
-                       (int64_t*)c->out_sum, nbins, INT64_MAX);
-    FH_CHECK(hipGetLastError());
-  }
-  if (OPS & B_PROD) {
-    int fb = (int)((nbins + 255) / 256);
-    if (c->vdtype == FH_F32 || c->vdtype == FH_F64)
-      hipLaunchKernelGGL(k_fill_f64, dim3(fb), dim3(256), 0, stream,
-                         (double*)c->out_sum, nbins, 1.0);
-    else
-      hipLaunchKernelGGL(k_fill_i64, dim3(fb), dim3(256), 0, stream,
-                         (int64_t*)c->out_sum, nbins, (int64_t)1);
-    FH_CHECK(hipGetLastError());
-  }
-  if (OPS & B_CNT) FH_CHECK(hipMemsetAsync(c->out_count, 0, nbins * 8, stream));
-  if (OPS & B_PRESENT) FH_CHECK(hipMemsetAsync(c->out_present, 0, nbins * 4, stream));
+  if (OPS & (B_SUM | B_SSD | B_WELFORD)) FH_CHECK(hipMemsetAsync(b.sum, 0, nbins * 8, stream));
+  if (OPS & B_WELFORD) FH_CHECK(hipMemsetAsync(b.sumx, 0, nbins * 8, stream));
+  if (OPS & (B_IDXMIN | B_ARGROW)) FH_CHECK(fill_bins(b.sum, nbins, (int64_t)INT64_MAX, stream));
+  if (OPS & B_IDXMAX) FH_CHECK(fill_bins(b.sum, nbins, (int64_t)-1, stream));
+  if (OPS & B_PROD) FH_CHECK(fill_bins(b.sum, nbins, (typename TR::Acc)1, stream));
+  if (OPS & B_CNT) FH_CHECK(hipMemsetAsync(b.cnt, 0, nbins * b.cnt_bytes, stream));
+  if (OPS & B_PRESENT) FH_CHECK(hipMemsetAsync(b.present, 0, nbins * 4, stream));
   if (OPS & B_MIN)
-    FH_CHECK(hipMemsetAsync(c->out_min, 0xFF, nbins * sizeof(typename TR::Enc), stream));
+    FH_CHECK(hipMemsetAsync(b.min, 0xFF, nbins * sizeof(typename TR::Enc), stream));
   if (OPS & B_MAX)
-    FH_CHECK(hipMemsetAsync(c->out_max, 0x00, nbins * sizeof(typename TR::Enc), stream));
-  if (OPS & B_NANFLAG) FH_CHECK(hipMemsetAsync(c->out_nanflag, 0, nbins * 4, stream));
+    FH_CHECK(hipMemsetAsync(b.max, 0x00, nbins * sizeof(typename TR::Enc), stream));
+  if (OPS & B_NANFLAG) FH_CHECK(hipMemsetAsync(b.nanflag, 0, nbins * 4, stream));
   return 0;
 }
 
-/* argrow phase launcher shared by the three partition variants */
-template <typename V, int OPS, typename PP>
-int launch_argrow_phase(fh_call* c, const PP& pp, const PairT<V>* pairs,
-                        const uint32_t* ends, uint32_t capF, int64_t maxspan,
-                        hipStream_t stream) {
-  if constexpr ((OPS & B_ARGROW) != 0 && sizeof(PairT<V>) == 16) {
-    const int skipnan = (c->flags & FH_SKIPNAN) ? 1 : 0;
-    const V* target = (const V*)((OPS & B_MIN) ? c->out_min : c->out_max);
-    const uint32_t* nan = skipnan ? nullptr : (const uint32_t*)c->out_nanflag;
-    const int64_t chunk = 1 << 19;
-    int maxchunks = (int)((maxspan + chunk - 1) / chunk);
-    if (maxchunks < 1) maxchunks = 1;
-    const int64_t lds = ((int64_t)pp.gpb * (sizeof(V) + 8) + 255) / 256 * 256;
-    auto kern = k_reduce_bucket_argrow<V>;
-    FH_CHECK(hipFuncSetAttribute((const void*)kern,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)lds));
-    hipLaunchKernelGGL(kern, dim3(maxchunks, pp.B), dim3(BLOCK_LDS), lds,
-                       stream, pairs, ends, capF, chunk, pp.gpb, pp.shift,
-                       c->ngroups, skipnan, target, nan, (int64_t*)c->out_sum);
+/* decode the output min/max bins in place */
+template <typename V, int OPS>
+int launch_decode(fh_call* c, int64_t nbins, hipStream_t stream) {
+  if (OPS & (B_MIN | B_MAX)) {
+    hipLaunchKernelGGL((k_decode<V, OPS>), dim3(grid_for(nbins)), dim3(256), 0,
+                       stream, nbins, c->out_min, c->out_max, c->out_count,
+                       c->out_present);
     FH_CHECK(hipGetLastError());
   }
   return 0;
 }
 
+/* ---- partition-path host plumbing ---------------------------------------- */
 struct PartPlan {
   int shift, gpb, B, Bpad;
   bool two_level;      /* B > 64: scatter via <= 64 super-buckets first */
@@ -1998,41 +1889,17 @@ struct PartPlan {
   int64_t overflow_off;
   uint32_t cap1, cap2; /* optimistic region strides (super / fine) */
   bool optimistic;     /* capacity regions fit u32 cursors */
-  int64_t scatter_lds, scatter2_lds;
+  int64_t tile_lds;    /* dynamic LDS of either scatter pass */
   bool feasible;
 };
-
-/* FH_PART_MODE: 0 auto (one-level direct scatter once two levels would be
- * needed), 1 force the two-level staged path, 2 force direct everywhere.
- * FH_PART_BINKB: pass-C LDS bin budget in KiB (default 150 of the CU's
- * 160; larger bins -> fewer, bigger buckets -> fewer reservation atomics). */
-inline int fh_part_mode() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("FH_PART_MODE");
-    v = e ? atoi(e) : 0;
-    if (v < 0 || v > 2) v = 0;
-  }
-  return v;
-}
-
-/* FH_PART_TILE: 0 (default) = full scatter staging tile (f32 6144 / f64
- * 3072 pairs, ~76 KB LDS, 2 blocks/CU); 1 = small tile (f32 4096 / f64
- * 2048, ~51/43 KB, 3 blocks/CU) — occupancy-vs-coalescing A/B knob. */
-inline int fh_part_tile() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("FH_PART_TILE");
-    v = (e && atoi(e) != 0) ? 1 : 0;
-  }
-  return v;
-}
 
 constexpr int64_t part_tile_lds(int T, int pairsz) {
   return (int64_t)(PART_SUB * PART_NW + PART_NW + 1 + PART_SUB + 3) * 4 +
          (int64_t)T * 4 + (int64_t)T * pairsz;
 }
 
+/* FH_PART_BINKB: pass-C LDS bin budget in KiB (larger bins -> fewer, bigger
+ * buckets -> fewer reservation atomics) */
 inline int64_t fh_part_bin_bytes() {
   static int64_t v = -1;
   if (v < 0) {
@@ -2075,12 +1942,8 @@ PartPlan part_plan(const fh_call* c) {
   const int bA = p.two_level ? p.B1 : p.B;
   if (bA > PART_SUB) return p; /* scatter passes handle <= 64 buckets */
   p.Bpad = PART_SUB;
-  constexpr int T = sizeof(V) == 4 ? 6144 : 3072;
-  const int64_t tile_lds = (int64_t)(PART_SUB * PART_NW + PART_NW + 1 + PART_SUB + 3) * 4 +
-                           (int64_t)T * 4 + (int64_t)T * sizeof(PairT<V>);
-  p.scatter_lds = tile_lds;
-  p.scatter2_lds = tile_lds;
-  if (p.scatter_lds > LDS_MAX) return p;
+  p.tile_lds = part_tile_lds(PART_TILE<V>, (int)sizeof(PairT<V>));
+  if (p.tile_lds > LDS_MAX) return p;
   /* optimistic capacity regions: uniform 25% + 8K rows of slack per bucket;
    * overflow (extreme skew) falls back to the exact counted path */
   auto cap_of = [&](int nb) {
@@ -2112,34 +1975,128 @@ PartPlan part_plan(const fh_call* c) {
   return p;
 }
 
+/* the plan's carve of the caller's scratch */
+template <typename V>
+struct PartScratch {
+  PairT<V> *pairs, *pairs2;
+  uint32_t *counts, *base, *baseA, *cursors, *overflow;
+};
+
+template <typename V>
+PartScratch<V> part_scratch(const fh_call* c, const PartPlan& pp) {
+  char* scr = (char*)c->scratch;
+  return {(PairT<V>*)(scr + pp.pairs_off),     (PairT<V>*)(scr + pp.pairs2_off),
+          (uint32_t*)(scr + pp.counts_off),    (uint32_t*)(scr + pp.base_off),
+          (uint32_t*)(scr + pp.baseA_off),     (uint32_t*)(scr + pp.cursors_off),
+          (uint32_t*)(scr + pp.overflow_off)};
+}
+
+/* one level of scattered buckets as the next stage reads it. cap == 0: the
+ * counted directory, bucket b is [ends[b], ends[b+1]). cap != 0: optimistic
+ * capacity regions, bucket b is [b*cap, ends[b]) with `ends` the cursors the
+ * scatter left behind. maxspan bounds any bucket's rows (it sizes the grid). */
+struct BucketDir {
+  const uint32_t* ends;
+  uint32_t cap;
+  int64_t maxspan;
+};
+
+/* pass 1: rows -> pairs, into the super-buckets when two-level, else the
+ * fine buckets. cursors[b] is bucket b's next free slot: a counted base
+ * (cap 0), or b*cap with writes past (b+1)*cap flagged in *overflow */
+template <typename V, typename L, bool CROW>
+int scatter_pass1(fh_call* c, const PartPlan& pp, uint32_t* cursors, uint32_t cap,
+                  uint32_t* overflow, PairT<V>* pairs, hipStream_t stream) {
+  auto kern = k_part_scatter<V, L, CROW>;
+  FH_CHECK(hipFuncSetAttribute((const void*)kern,
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)pp.tile_lds));
+  const int shA = pp.two_level ? pp.shift + 6 : pp.shift;
+  const int bA = pp.two_level ? pp.B1 : pp.B;
+  hipLaunchKernelGGL(kern, dim3(capped_grid(c->n, PART_TILE<V>, 1024)),
+                     dim3(PART_BLOCK), pp.tile_lds, stream, (const V*)c->values,
+                     (const L*)c->labels, (const L*)c->labels2, c->n, c->ngroups,
+                     c->g0, c->g1, shA, bA, pp.Bpad, cursors, cap, overflow,
+                     pairs, c->row_offset);
+  FH_CHECK(hipGetLastError());
+  return 0;
+}
+
+/* pass 2 (two-level only): each super-bucket of `in` -> its <= 64 fine
+ * buckets in `out`; cursors/cap2 as in pass 1 */
+template <typename V, bool CROW>
+int scatter_pass2(const PartPlan& pp, const PairT<V>* in, const BucketDir& super,
+                  uint32_t* cursors, uint32_t cap2, uint32_t* overflow,
+                  PairT<V>* out, hipStream_t stream) {
+  auto kern = k_part_scatter2<V, CROW>;
+  FH_CHECK(hipFuncSetAttribute((const void*)kern,
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)pp.tile_lds));
+  const int tiles_x = capped_grid(super.maxspan, PART_TILE<V>, 64);
+  hipLaunchKernelGGL(kern, dim3(tiles_x, pp.B1), dim3(PART_BLOCK), pp.tile_lds,
+                     stream, in, super.ends, super.cap, pp.shift, pp.B, cursors,
+                     cap2, overflow, out);
+  FH_CHECK(hipGetLastError());
+  return 0;
+}
+
+/* pass C: identity-fill the outputs, reduce every fine bucket in LDS, decode
+ * min/max, then the arg-pair sets' matching-row phase */
+template <typename V, int OPS>
+int reduce_buckets(fh_call* c, const PartPlan& pp, const PairT<V>* pairs,
+                   const BucketDir& fine, hipStream_t stream) {
+  const int skipnan = (c->flags & FH_SKIPNAN) ? 1 : 0;
+  const int64_t chunk = 1 << 19;
+  const int maxchunks = capped_grid(fine.maxspan, chunk, INT32_MAX);
+  FH_TRY((init_bins<V, OPS>(out_bins(c), c->ngroups, stream)));
+  auto kern = k_reduce_bucket<V, OPS>;
+  FH_CHECK(hipFuncSetAttribute((const void*)kern,
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)pp.lay.bytes));
+  hipLaunchKernelGGL(kern, dim3(maxchunks, pp.B), dim3(BLOCK_LDS), pp.lay.bytes,
+                     stream, pairs, fine.ends, fine.cap, chunk, pp.gpb, pp.shift,
+                     c->ngroups, c->means, skipnan, pp.lay, c->out_sum,
+                     c->out_count, c->out_present, c->out_min, c->out_max,
+                     c->out_nanflag);
+  FH_CHECK(hipGetLastError());
+  FH_TRY((launch_decode<V, OPS>(c, c->ngroups, stream)));
+  if constexpr ((OPS & B_ARGROW) != 0 && sizeof(PairT<V>) == 16) {
+    const V* target = (const V*)((OPS & B_MIN) ? c->out_min : c->out_max);
+    const uint32_t* nan = skipnan ? nullptr : (const uint32_t*)c->out_nanflag;
+    const int64_t lds = ((int64_t)pp.gpb * (sizeof(V) + 8) + 255) / 256 * 256;
+    auto arg = k_reduce_bucket_argrow<V>;
+    FH_CHECK(hipFuncSetAttribute((const void*)arg,
+                                 hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)lds));
+    hipLaunchKernelGGL(arg, dim3(maxchunks, pp.B), dim3(BLOCK_LDS), lds, stream,
+                       pairs, fine.ends, fine.cap, chunk, pp.gpb, pp.shift,
+                       c->ngroups, skipnan, target, nan, (int64_t*)c->out_sum);
+    FH_CHECK(hipGetLastError());
+  }
+  return 0;
+}
+
+/* exact partition: a counting pre-pass and a host-built bucket directory
+ * give every bucket its true extent (cap 0 throughout) */
 template <typename V, typename L, int OPS>
 int launch_partition_exact(fh_call* c, const PartPlan& pp) {
   hipStream_t stream = (hipStream_t)c->stream;
-  const int skipnan = (c->flags & FH_SKIPNAN) ? 1 : 0;
   constexpr bool CROW = (OPS & B_ARGROW) != 0 && sizeof(PairT<V>) == 16;
-  char* scr = (char*)c->scratch;
-  uint32_t* overflow = (uint32_t*)(scr + pp.overflow_off);
-  uint32_t* counts = (uint32_t*)(scr + pp.counts_off);
-  uint32_t* based = (uint32_t*)(scr + pp.base_off);
-  uint32_t* baseAd = (uint32_t*)(scr + pp.baseA_off);
-  uint32_t* cursors = (uint32_t*)(scr + pp.cursors_off);
-  PairT<V>* pairs = (PairT<V>*)(scr + pp.pairs_off);
-  PairT<V>* pairs2 = (PairT<V>*)(scr + pp.pairs2_off);
+  const PartScratch<V> s = part_scratch<V>(c, pp);
 
-  FH_CHECK(hipMemsetAsync(counts, 0, (int64_t)pp.B * 4, stream));
+  FH_CHECK(hipMemsetAsync(s.counts, 0, (int64_t)pp.B * 4, stream));
   {
-    int64_t wb = (c->n + 255) / 256;
-    int nb0 = (int)(wb < 2048 ? (wb > 0 ? wb : 1) : 2048);
     /* the count pass histograms the FINE buckets (up to 4096) */
     const int64_t hist_lds = ((int64_t)pp.B + 63) / 64 * 64 * 4;
-    hipLaunchKernelGGL((k_part_count<L>), dim3(nb0), dim3(256), hist_lds,
-                       stream, (const L*)c->labels, (const L*)c->labels2, c->n,
-                       c->ngroups, c->g0, c->g1, pp.shift, pp.B, counts);
+    hipLaunchKernelGGL((k_part_count<L>), dim3(capped_grid(c->n, 256, 2048)),
+                       dim3(256), hist_lds, stream, (const L*)c->labels,
+                       (const L*)c->labels2, c->n, c->ngroups, c->g0, c->g1,
+                       pp.shift, pp.B, s.counts);
     FH_CHECK(hipGetLastError());
   }
   /* bucket directory on the host (one sync; B <= 4096 words) */
   static thread_local uint32_t h_counts[4096], h_base[4097];
-  FH_CHECK(hipMemcpyAsync(h_counts, counts, (int64_t)pp.B * 4,
+  FH_CHECK(hipMemcpyAsync(h_counts, s.counts, (int64_t)pp.B * 4,
                           hipMemcpyDeviceToHost, stream));
   FH_CHECK(hipStreamSynchronize(stream));
   uint32_t acc = 0, maxc = 0;
@@ -2149,7 +2106,7 @@ int launch_partition_exact(fh_call* c, const PartPlan& pp) {
     if (h_counts[i] > maxc) maxc = h_counts[i];
   }
   h_base[pp.B] = acc;
-  FH_CHECK(hipMemcpyAsync(based, h_base, ((int64_t)pp.B + 1) * 4,
+  FH_CHECK(hipMemcpyAsync(s.base, h_base, ((int64_t)pp.B + 1) * 4,
                           hipMemcpyHostToDevice, stream));
   /* super-bucket directory: sums of PART_SUB fine buckets */
   static thread_local uint32_t h_baseA[4097];
@@ -2163,303 +2120,116 @@ int launch_partition_exact(fh_call* c, const PartPlan& pp) {
       const uint32_t cnt = h_baseA[sbi + 1] - h_baseA[sbi];
       if (cnt > maxA) maxA = cnt;
     }
-    FH_CHECK(hipMemcpyAsync(baseAd, h_baseA, ((int64_t)pp.B1 + 1) * 4,
-                            hipMemcpyHostToDevice, stream));
-    /* pass-A cursors: super-bucket bases (first B1 words of cursors) */
-    FH_CHECK(hipMemcpyAsync(cursors, h_baseA, (int64_t)pp.B1 * 4,
-                            hipMemcpyHostToDevice, stream));
-  } else {
-    FH_CHECK(hipMemcpyAsync(cursors, h_base, (int64_t)pp.B * 4,
+    FH_CHECK(hipMemcpyAsync(s.baseA, h_baseA, ((int64_t)pp.B1 + 1) * 4,
                             hipMemcpyHostToDevice, stream));
   }
-
-  {
-    const int shA = pp.two_level ? pp.shift + 6 : pp.shift;
-    const int bA = pp.two_level ? pp.B1 : pp.B;
-    auto launch1 = [&](auto tc) {
-      constexpr int T = decltype(tc)::value;
-      auto kern = k_part_scatter<V, L, CROW, T>;
-      const int64_t lds = part_tile_lds(T, (int)sizeof(PairT<V>));
-      hipError_t e = hipFuncSetAttribute(
-          (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-          (int)lds);
-      if (e != hipSuccess) return e;
-      int64_t wb = (c->n + T - 1) / T;
-      int nb1 = (int)(wb < 1024 ? (wb > 0 ? wb : 1) : 1024);
-      hipLaunchKernelGGL(kern, dim3(nb1), dim3(PART_BLOCK), lds, stream,
-                         (const V*)c->values, (const L*)c->labels,
-                         (const L*)c->labels2, c->n, c->ngroups, c->g0, c->g1,
-                         shA, bA, pp.Bpad, cursors, 0u, overflow, pairs,
-                         c->row_offset);
-      return hipGetLastError();
-    };
-    hipError_t e1;
-    if (fh_part_tile())
-      e1 = launch1(std::integral_constant<int, (sizeof(V) == 4 ? 4096 : 2048)>{});
-    else
-      e1 = launch1(std::integral_constant<int, (sizeof(V) == 4 ? 6144 : 3072)>{});
-    FH_CHECK(e1);
-  }
+  /* pass-1 cursors: the bases of the buckets it scatters into */
+  FH_CHECK(hipMemcpyAsync(s.cursors, pp.two_level ? h_baseA : h_base,
+                          (int64_t)(pp.two_level ? pp.B1 : pp.B) * 4,
+                          hipMemcpyHostToDevice, stream));
+  FH_TRY((scatter_pass1<V, L, CROW>(c, pp, s.cursors, 0u, s.overflow, s.pairs, stream)));
   if (pp.two_level) {
     /* fine-bucket cursors, then the in-super-bucket scatter */
-    FH_CHECK(hipMemcpyAsync(cursors, h_base, (int64_t)pp.B * 4,
+    FH_CHECK(hipMemcpyAsync(s.cursors, h_base, (int64_t)pp.B * 4,
                             hipMemcpyHostToDevice, stream));
-    auto launch2 = [&](auto tc) {
-      constexpr int T = decltype(tc)::value;
-      auto kern2 = k_part_scatter2<V, CROW, T>;
-      const int64_t lds = part_tile_lds(T, (int)sizeof(PairT<V>));
-      hipError_t e = hipFuncSetAttribute(
-          (const void*)kern2, hipFuncAttributeMaxDynamicSharedMemorySize,
-          (int)lds);
-      if (e != hipSuccess) return e;
-      int tiles_x = (int)((maxA + T - 1) / T);
-      if (tiles_x > 64) tiles_x = 64;
-      if (tiles_x < 1) tiles_x = 1;
-      hipLaunchKernelGGL(kern2, dim3(tiles_x, pp.B1), dim3(PART_BLOCK), lds,
-                         stream, pairs, baseAd, 0u, pp.shift,
-                         pp.B, cursors, 0u, overflow, pairs2);
-      return hipGetLastError();
-    };
-    hipError_t e2;
-    if (fh_part_tile())
-      e2 = launch2(std::integral_constant<int, (sizeof(V) == 4 ? 4096 : 2048)>{});
-    else
-      e2 = launch2(std::integral_constant<int, (sizeof(V) == 4 ? 6144 : 3072)>{});
-    FH_CHECK(e2);
+    FH_TRY((scatter_pass2<V, CROW>(pp, s.pairs, BucketDir{s.baseA, 0u, (int64_t)maxA},
+                                   s.cursors, 0u, s.overflow, s.pairs2, stream)));
   }
-  {
-    int rc = init_outs<V, OPS>(c, c->ngroups, stream);
-    if (rc) return rc;
-  }
-  {
-    auto kern = k_reduce_bucket<V, OPS>;
-    FH_CHECK(hipFuncSetAttribute((const void*)kern,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)pp.lay.bytes));
-    const int64_t chunk = 1 << 19;
-    int maxchunks = (int)((maxc + chunk - 1) / chunk);
-    if (maxchunks < 1) maxchunks = 1;
-    hipLaunchKernelGGL(kern, dim3(maxchunks, pp.B), dim3(BLOCK_LDS),
-                       pp.lay.bytes, stream, pp.two_level ? pairs2 : pairs,
-                       based, 0u, chunk, pp.gpb, pp.shift, c->ngroups, c->means,
-                       skipnan, pp.lay, c->out_sum, c->out_count,
-                       c->out_present, c->out_min, c->out_max, c->out_nanflag);
-    FH_CHECK(hipGetLastError());
-  }
-  if (OPS & (B_MIN | B_MAX)) {
-    int db = (int)((c->ngroups + 255) / 256);
-    hipLaunchKernelGGL((k_decode<V, OPS>), dim3(db), dim3(256), 0, stream,
-                       c->ngroups, c->out_min, c->out_max, c->out_count,
-                       c->out_present);
-    FH_CHECK(hipGetLastError());
-  }
-  {
-    int rc = launch_argrow_phase<V, OPS>(c, pp, pp.two_level ? pairs2 : pairs,
-                                         based, 0u, (int64_t)maxc, stream);
-    if (rc) return rc;
-  }
+  FH_TRY((reduce_buckets<V, OPS>(c, pp, pp.two_level ? s.pairs2 : s.pairs,
+                                 BucketDir{s.base, 0u, (int64_t)maxc}, stream)));
   c->path_used = 4;
   return 0;
 }
 
-/* one-level direct partition (optimistic): scatter straight into the
- * fine-bucket capacity regions with k_part_scatter_direct — no second
- * scatter pass and no LDS staging — then the per-bucket LDS-binned
- * reduce. ~28 B/row streamed vs the two-level's ~44. Overflow falls back
- * to the exact two-level path (the scratch keeps its layout). */
-template <typename V, typename L, int OPS>
-int launch_partition_direct(fh_call* c, const PartPlan& pp) {
-  hipStream_t stream = (hipStream_t)c->stream;
-  const int skipnan = (c->flags & FH_SKIPNAN) ? 1 : 0;
-  constexpr bool CROW = (OPS & B_ARGROW) != 0 && sizeof(PairT<V>) == 16;
-  char* scr = (char*)c->scratch;
-  uint32_t* cursors = (uint32_t*)(scr + pp.cursors_off);
-  uint32_t* overflow = (uint32_t*)(scr + pp.overflow_off);
-  PairT<V>* pairs2 = (PairT<V>*)(scr + pp.pairs2_off);
-
-  FH_CHECK(hipMemsetAsync(overflow, 0, 4, stream));
-  hipLaunchKernelGGL(k_init_cursors, dim3((pp.B + 255) / 256), dim3(256), 0,
-                     stream, cursors, pp.B, pp.cap2);
-  FH_CHECK(hipGetLastError());
-  {
-    auto kern = k_part_scatter_direct<V, L, CROW>;
-    const int64_t hist_lds = ((int64_t)pp.B + 63) / 64 * 64 * 4;
-    FH_CHECK(hipFuncSetAttribute((const void*)kern,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)hist_lds));
-    constexpr int T = PBD * (sizeof(V) == 4 ? 24 : 12);
-    int64_t wb = (c->n + T - 1) / T;
-    int nb = (int)(wb < 1536 ? (wb > 0 ? wb : 1) : 1536);
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(PBD), hist_lds, stream,
-                       (const V*)c->values, (const L*)c->labels,
-                       (const L*)c->labels2, c->n, c->ngroups, c->g0, c->g1,
-                       pp.shift, pp.B, cursors, pp.cap2, overflow, pairs2,
-                       c->row_offset);
-    FH_CHECK(hipGetLastError());
-  }
-  {
-    int rc = init_outs<V, OPS>(c, c->ngroups, stream);
-    if (rc) return rc;
-  }
-  {
-    auto kern = k_reduce_bucket<V, OPS>;
-    FH_CHECK(hipFuncSetAttribute((const void*)kern,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)pp.lay.bytes));
-    const int64_t chunk = 1 << 19;
-    int maxchunks = (int)(((int64_t)pp.cap2 + chunk - 1) / chunk);
-    if (maxchunks < 1) maxchunks = 1;
-    hipLaunchKernelGGL(kern, dim3(maxchunks, pp.B), dim3(BLOCK_LDS),
-                       pp.lay.bytes, stream, pairs2, cursors, pp.cap2, chunk,
-                       pp.gpb, pp.shift, c->ngroups, c->means, skipnan, pp.lay,
-                       c->out_sum, c->out_count, c->out_present, c->out_min,
-                       c->out_max, c->out_nanflag);
-    FH_CHECK(hipGetLastError());
-  }
-  if (OPS & (B_MIN | B_MAX)) {
-    int db = (int)((c->ngroups + 255) / 256);
-    hipLaunchKernelGGL((k_decode<V, OPS>), dim3(db), dim3(256), 0, stream,
-                       c->ngroups, c->out_min, c->out_max, c->out_count,
-                       c->out_present);
-    FH_CHECK(hipGetLastError());
-  }
-  {
-    int rc = launch_argrow_phase<V, OPS>(c, pp, pairs2, cursors, pp.cap2,
-                                         (int64_t)pp.cap2, stream);
-    if (rc) return rc;
-  }
-  uint32_t h_ov = 0;
-  FH_CHECK(hipMemcpyAsync(&h_ov, overflow, 4, hipMemcpyDeviceToHost, stream));
-  FH_CHECK(hipStreamSynchronize(stream));
-  if (h_ov) return launch_partition_exact<V, L, OPS>(c, pp);
-  c->path_used = 6;
-  return 0;
-}
-
 /* optimistic partition: capacity regions replace the counting pre-pass and
- * every host round trip except the final 4-byte overflow check */
+ * every host round trip except the final 4-byte overflow check. (A one-level
+ * direct scatter into all fine buckets was measured and rejected:
+ * profiles/r02_direct_pmc.md, 3.5x write amplification.) */
 template <typename V, typename L, int OPS>
 int launch_partition(fh_call* c, const PartPlan& pp) {
   if (!pp.optimistic) return launch_partition_exact<V, L, OPS>(c, pp);
-  constexpr bool CROW = (OPS & B_ARGROW) != 0 && sizeof(PairT<V>) == 16;
-  /* The one-level direct variant is kept for evidence (FH_PART_MODE=2) but
-   * is NOT the default: measured on MI355X (profiles/r02_direct_pmc.md) its
-   * partial-line scatter stores amplify 3.5x (WRITE_SIZE 28.1 GB for 8 GB
-   * of pairs) and the ~1e8 reservation atomics add fabric RMW, so its
-   * effective traffic exceeds the staged two-level's 44 GB/row-stream. */
-  if (fh_part_mode() == 2) return launch_partition_direct<V, L, OPS>(c, pp);
   hipStream_t stream = (hipStream_t)c->stream;
-  const int skipnan = (c->flags & FH_SKIPNAN) ? 1 : 0;
-  char* scr = (char*)c->scratch;
-  uint32_t* cursorsA = (uint32_t*)(scr + pp.counts_off); /* reused slot */
-  uint32_t* cursors = (uint32_t*)(scr + pp.cursors_off);
-  uint32_t* overflow = (uint32_t*)(scr + pp.overflow_off);
-  PairT<V>* pairs = (PairT<V>*)(scr + pp.pairs_off);
-  PairT<V>* pairs2 = (PairT<V>*)(scr + pp.pairs2_off);
+  constexpr bool CROW = (OPS & B_ARGROW) != 0 && sizeof(PairT<V>) == 16;
+  const PartScratch<V> s = part_scratch<V>(c, pp);
 
-  FH_CHECK(hipMemsetAsync(overflow, 0, 4, stream));
+  FH_CHECK(hipMemsetAsync(s.overflow, 0, 4, stream));
+  uint32_t* cursorsA = s.counts; /* reused slot */
   const int bA = pp.two_level ? pp.B1 : pp.B;
   const uint32_t capA = pp.two_level ? pp.cap1 : pp.cap2;
   hipLaunchKernelGGL(k_init_cursors, dim3(1), dim3(PART_SUB), 0, stream,
                      cursorsA, bA, capA);
   FH_CHECK(hipGetLastError());
-  {
-    const int shA = pp.two_level ? pp.shift + 6 : pp.shift;
-    auto launch1 = [&](auto tc) {
-      constexpr int T = decltype(tc)::value;
-      auto kern = k_part_scatter<V, L, CROW, T>;
-      const int64_t lds = part_tile_lds(T, (int)sizeof(PairT<V>));
-      hipError_t e = hipFuncSetAttribute(
-          (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-          (int)lds);
-      if (e != hipSuccess) return e;
-      int64_t wb = (c->n + T - 1) / T;
-      int nb1 = (int)(wb < 1024 ? (wb > 0 ? wb : 1) : 1024);
-      hipLaunchKernelGGL(kern, dim3(nb1), dim3(PART_BLOCK), lds, stream,
-                         (const V*)c->values, (const L*)c->labels,
-                         (const L*)c->labels2, c->n, c->ngroups, c->g0, c->g1,
-                         shA, bA, pp.Bpad, cursorsA, capA, overflow, pairs,
-                         c->row_offset);
-      return hipGetLastError();
-    };
-    hipError_t e1;
-    if (fh_part_tile())
-      e1 = launch1(std::integral_constant<int, (sizeof(V) == 4 ? 4096 : 2048)>{});
-    else
-      e1 = launch1(std::integral_constant<int, (sizeof(V) == 4 ? 6144 : 3072)>{});
-    FH_CHECK(e1);
-  }
+  FH_TRY((scatter_pass1<V, L, CROW>(c, pp, cursorsA, capA, s.overflow, s.pairs, stream)));
+  BucketDir fine{cursorsA, capA, (int64_t)capA};
   if (pp.two_level) {
-    hipLaunchKernelGGL(k_init_cursors, dim3((pp.B + 255) / 256), dim3(256), 0,
-                       stream, cursors, pp.B, pp.cap2);
+    hipLaunchKernelGGL(k_init_cursors, dim3(grid_for(pp.B)), dim3(256), 0,
+                       stream, s.cursors, pp.B, pp.cap2);
     FH_CHECK(hipGetLastError());
-    auto launch2 = [&](auto tc) {
-      constexpr int T = decltype(tc)::value;
-      auto kern2 = k_part_scatter2<V, CROW, T>;
-      const int64_t lds = part_tile_lds(T, (int)sizeof(PairT<V>));
-      hipError_t e = hipFuncSetAttribute(
-          (const void*)kern2, hipFuncAttributeMaxDynamicSharedMemorySize,
-          (int)lds);
-      if (e != hipSuccess) return e;
-      int tiles_x = (int)(((int64_t)pp.cap1 + T - 1) / T);
-      if (tiles_x > 64) tiles_x = 64;
-      if (tiles_x < 1) tiles_x = 1;
-      hipLaunchKernelGGL(kern2, dim3(tiles_x, pp.B1), dim3(PART_BLOCK), lds,
-                         stream, pairs, cursorsA, pp.cap1,
-                         pp.shift, pp.B, cursors, pp.cap2, overflow, pairs2);
-      return hipGetLastError();
-    };
-    hipError_t e2;
-    if (fh_part_tile())
-      e2 = launch2(std::integral_constant<int, (sizeof(V) == 4 ? 4096 : 2048)>{});
-    else
-      e2 = launch2(std::integral_constant<int, (sizeof(V) == 4 ? 6144 : 3072)>{});
-    FH_CHECK(e2);
+    FH_TRY((scatter_pass2<V, CROW>(pp, s.pairs, fine, s.cursors, pp.cap2,
+                                   s.overflow, s.pairs2, stream)));
+    fine = BucketDir{s.cursors, pp.cap2, (int64_t)pp.cap2};
   }
-  {
-    int rc = init_outs<V, OPS>(c, c->ngroups, stream);
-    if (rc) return rc;
-  }
-  {
-    auto kern = k_reduce_bucket<V, OPS>;
-    FH_CHECK(hipFuncSetAttribute((const void*)kern,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)pp.lay.bytes));
-    const int64_t chunk = 1 << 19;
-    const uint32_t capF = pp.cap2;
-    int maxchunks = (int)(((int64_t)capF + chunk - 1) / chunk);
-    if (maxchunks < 1) maxchunks = 1;
-    hipLaunchKernelGGL(kern, dim3(maxchunks, pp.B), dim3(BLOCK_LDS),
-                       pp.lay.bytes, stream,
-                       pp.two_level ? pairs2 : pairs,
-                       pp.two_level ? cursors : cursorsA, capF, chunk, pp.gpb,
-                       pp.shift, c->ngroups, c->means, skipnan, pp.lay,
-                       c->out_sum, c->out_count, c->out_present, c->out_min,
-                       c->out_max, c->out_nanflag);
-    FH_CHECK(hipGetLastError());
-  }
-  if (OPS & (B_MIN | B_MAX)) {
-    int db = (int)((c->ngroups + 255) / 256);
-    hipLaunchKernelGGL((k_decode<V, OPS>), dim3(db), dim3(256), 0, stream,
-                       c->ngroups, c->out_min, c->out_max, c->out_count,
-                       c->out_present);
-    FH_CHECK(hipGetLastError());
-  }
-  {
-    int rc = launch_argrow_phase<V, OPS>(
-        c, pp, pp.two_level ? pairs2 : pairs,
-        pp.two_level ? cursors : cursorsA, pp.cap2, (int64_t)pp.cap2, stream);
-    if (rc) return rc;
-  }
+  FH_TRY((reduce_buckets<V, OPS>(c, pp, pp.two_level ? s.pairs2 : s.pairs, fine, stream)));
   uint32_t h_ov = 0;
-  FH_CHECK(hipMemcpyAsync(&h_ov, overflow, 4, hipMemcpyDeviceToHost, stream));
+  FH_CHECK(hipMemcpyAsync(&h_ov, s.overflow, 4, hipMemcpyDeviceToHost, stream));
   FH_CHECK(hipStreamSynchronize(stream));
   if (h_ov) return launch_partition_exact<V, L, OPS>(c, pp);
   c->path_used = 4;
   return 0;
 }
 
+/* sorted-labels direct path: skip every scatter pass — each bucket's rows
+ * are already a contiguous range of the original arrays. Returns -1 when the
+ * path does not apply to this call. */
+template <typename V, typename L, int OPS>
+int launch_sorted_direct(fh_call* c) {
+  if (!(c->flags & FH_SORTED_LABELS) || c->labels2 ||
+      (c->flags & FH_FORCE_ATOMIC) || (OPS & (B_IDXMIN | B_IDXMAX)))
+    return -1;
+  const PartPlan pp = part_plan<V>(c);
+  if (!pp.feasible || c->scratch_bytes < (int64_t)(pp.B + 1) * 4) return -1;
+  hipStream_t stream = (hipStream_t)c->stream;
+  const bool skipnan = (c->flags & FH_SKIPNAN) != 0;
+  uint32_t* base = (uint32_t*)c->scratch;
+  hipLaunchKernelGGL((k_bucket_bounds<L>), dim3(grid_for(pp.B + 1)), dim3(256),
+                     0, stream, (const L*)c->labels, c->n, pp.B, pp.shift, base);
+  FH_CHECK(hipGetLastError());
+  FH_TRY((init_bins<V, OPS>(out_bins(c), c->ngroups, stream)));
+  auto kern = k_reduce_bucket_direct<V, L, OPS>;
+  FH_CHECK(hipFuncSetAttribute((const void*)kern,
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)pp.lay.bytes));
+  const int64_t chunk = 1 << 19;
+  int nchunks = (int)((c->n / pp.B + chunk) / chunk) + 1;
+  if (nchunks > 16) nchunks = 16;
+  hipLaunchKernelGGL(kern, dim3(nchunks, pp.B), dim3(BLOCK_LDS), pp.lay.bytes,
+                     stream, (const V*)c->values, (const L*)c->labels, base,
+                     chunk, pp.gpb, pp.shift, c->ngroups, c->means, skipnan,
+                     pp.lay, c->out_sum, c->out_count, c->out_present,
+                     c->out_min, c->out_max, c->out_nanflag);
+  FH_CHECK(hipGetLastError());
+  FH_TRY((launch_decode<V, OPS>(c, c->ngroups, stream)));
+  c->path_used = 5;
+  return 0;
+}
+
 /* ---- host-side dispatch -------------------------------------------------- */
+
+/* do the per-block bins of an op set fit LDS, and how many blocks per CU */
+struct LdsPlan {
+  BinLayout lay;
+  bool fits;
+  int blocks_per_cu;
+};
+
+template <typename V>
+LdsPlan lds_plan(int bits, int64_t ngroups) {
+  LdsPlan p{};
+  p.lay = bin_layout<V>(bits, ngroups, 4);
+  p.fits = p.lay.bytes <= LDS_MAX;
+  p.blocks_per_cu = p.lay.bytes * 2 <= LDS_MAX ? 2 : 1;
+  return p;
+}
 
 /* everything past the LDS-binned path: sorted-direct, bucket partition,
  * global atomics (never instantiated for uint16 code labels) */
@@ -2470,43 +2240,9 @@ int launch_beyond_lds(fh_call* c) {
   const bool skipnan = (c->flags & FH_SKIPNAN) != 0;
   if (c->emit_codes) return 13; /* codes are emitted by the LDS kernel only */
 
-  /* sorted-labels direct path: skip every scatter pass — each bucket's rows
-   * are already a contiguous range of the original arrays */
-  if ((c->flags & FH_SORTED_LABELS) && !c->labels2 &&
-      !(c->flags & FH_FORCE_ATOMIC) && !(OPS & (B_IDXMIN | B_IDXMAX))) {
-    PartPlan pp = part_plan<V>(c);
-    if (pp.feasible && c->scratch_bytes >= (int64_t)(pp.B + 1) * 4) {
-      uint32_t* base = (uint32_t*)c->scratch;
-      const int bb = (pp.B + 256) / 256;
-      hipLaunchKernelGGL((k_bucket_bounds<L>), dim3(bb), dim3(256), 0, stream,
-                         (const L*)c->labels, c->n, pp.B, pp.shift, base);
-      FH_CHECK(hipGetLastError());
-      int rc = init_outs<V, OPS>(c, c->ngroups, stream);
-      if (rc) return rc;
-      auto kern = k_reduce_bucket_direct<V, L, OPS>;
-      FH_CHECK(hipFuncSetAttribute((const void*)kern,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)pp.lay.bytes));
-      const int64_t chunk = 1 << 19;
-      int nchunks = (int)((c->n / pp.B + chunk) / chunk) + 1;
-      if (nchunks > 16) nchunks = 16;
-      hipLaunchKernelGGL(kern, dim3(nchunks, pp.B), dim3(BLOCK_LDS),
-                         pp.lay.bytes, stream, (const V*)c->values,
-                         (const L*)c->labels, base, chunk, pp.gpb, pp.shift,
-                         c->ngroups, c->means, skipnan, pp.lay, c->out_sum,
-                         c->out_count, c->out_present, c->out_min, c->out_max,
-                         c->out_nanflag);
-      FH_CHECK(hipGetLastError());
-      if (OPS & (B_MIN | B_MAX)) {
-        int db = (int)((c->ngroups + 255) / 256);
-        hipLaunchKernelGGL((k_decode<V, OPS>), dim3(db), dim3(256), 0, stream,
-                           c->ngroups, c->out_min, c->out_max, c->out_count,
-                           c->out_present);
-        FH_CHECK(hipGetLastError());
-      }
-      c->path_used = 5;
-      return 0;
-    }
+  {
+    const int rc = launch_sorted_direct<V, L, OPS>(c);
+    if (rc >= 0) return rc;
   }
 
   /* huge group counts: bucket-partition path when scratch allows. Not
@@ -2519,38 +2255,10 @@ int launch_beyond_lds(fh_call* c) {
       return launch_partition<V, L, OPS>(c, pp);
   }
 
-  /* global-atomic path: memset-style init of the bins */
-  const int64_t ng = c->ngroups;
-  if (OPS & (B_SUM | B_SSD))
-    FH_CHECK(hipMemsetAsync(c->out_sum, 0, ng * 8, stream));
-  if (OPS & (B_IDXMIN | B_IDXMAX)) {
-    int fb = (int)((ng + 255) / 256);
-    hipLaunchKernelGGL(k_fill_i64, dim3(fb), dim3(256), 0, stream,
-                       (int64_t*)c->out_sum, ng,
-                       (OPS & B_IDXMIN) ? INT64_MAX : (int64_t)-1);
-    FH_CHECK(hipGetLastError());
-  }
-  if (OPS & B_PROD) {
-    int fb = (int)((ng + 255) / 256);
-    if (c->vdtype == FH_F32 || c->vdtype == FH_F64)
-      hipLaunchKernelGGL(k_fill_f64, dim3(fb), dim3(256), 0, stream,
-                         (double*)c->out_sum, ng, 1.0);
-    else
-      hipLaunchKernelGGL(k_fill_i64, dim3(fb), dim3(256), 0, stream,
-                         (int64_t*)c->out_sum, ng, (int64_t)1);
-    FH_CHECK(hipGetLastError());
-  }
-  if (OPS & B_CNT) FH_CHECK(hipMemsetAsync(c->out_count, 0, ng * 8, stream));
-  if (OPS & B_PRESENT) FH_CHECK(hipMemsetAsync(c->out_present, 0, ng * 4, stream));
-  if (OPS & B_MIN)
-    FH_CHECK(hipMemsetAsync(c->out_min, 0xFF, ng * sizeof(typename TR::Enc), stream));
-  if (OPS & B_MAX)
-    FH_CHECK(hipMemsetAsync(c->out_max, 0x00, ng * sizeof(typename TR::Enc), stream));
-  if (OPS & B_NANFLAG) FH_CHECK(hipMemsetAsync(c->out_nanflag, 0, ng * 4, stream));
-
-  int64_t work_blocks = (c->n / TR::VEC + BLOCK_ATOMIC - 1) / BLOCK_ATOMIC;
-  int nblocks = (int)(work_blocks < 2048 ? (work_blocks > 0 ? work_blocks : 1) : 2048);
-  hipLaunchKernelGGL((k_reduce_atomic<V, L, OPS>), dim3(nblocks),
+  /* global-atomic path */
+  FH_TRY((init_bins<V, OPS>(out_bins(c), c->ngroups, stream)));
+  hipLaunchKernelGGL((k_reduce_atomic<V, L, OPS>),
+                     dim3(capped_grid(c->n / TR::VEC, BLOCK_ATOMIC, 2048)),
                      dim3(BLOCK_ATOMIC), 0, stream, (const V*)c->values,
                      (const L*)c->labels, (const L*)c->labels2, c->n, c->ngroups,
                      c->g0, c->g1, c->means, (const V*)c->target, c->row_offset,
@@ -2558,12 +2266,7 @@ int launch_beyond_lds(fh_call* c) {
                      c->out_count, c->out_present, c->out_min, c->out_max,
                      c->out_nanflag);
   FH_CHECK(hipGetLastError());
-  if (OPS & (B_MIN | B_MAX)) {
-    int db = (int)((ng + 255) / 256);
-    hipLaunchKernelGGL((k_decode<V, OPS>), dim3(db), dim3(256), 0, stream, ng,
-                       c->out_min, c->out_max, c->out_count, c->out_present);
-    FH_CHECK(hipGetLastError());
-  }
+  FH_TRY((launch_decode<V, OPS>(c, c->ngroups, stream)));
   c->path_used = 2;
   return 0;
 }
@@ -2572,13 +2275,14 @@ template <typename V, typename L, int OPS>
 int launch_typed(fh_call* c) {
   hipStream_t stream = (hipStream_t)c->stream;
   const bool skipnan = (c->flags & FH_SKIPNAN) != 0;
-  BinLayout lay = bin_layout<V>(OPS, c->ngroups, 4);
+  const LdsPlan lp = lds_plan<V>(OPS, c->ngroups);
+  const BinLayout& lay = lp.lay;
   constexpr bool U16 = std::is_same<L, uint16_t>::value;
 
   if (c->finish) {
     /* a finish mode is served by the LDS path's combine only: refuse rather
      * than hand back partials the caller did not allocate */
-    if (c->finish != finish_of(OPS) || lay.bytes > LDS_MAX ||
+    if (c->finish != finish_of(OPS) || !lp.fits ||
         (c->flags & FH_FORCE_ATOMIC) || !c->result ||
         (c->result_dtype != FH_F32 && c->result_dtype != FH_F64 &&
          c->result_dtype != FH_I64) ||
@@ -2588,14 +2292,14 @@ int launch_typed(fh_call* c) {
 
   if constexpr ((OPS & B_MOM2) != 0) {
     /* the summary set exists on the LDS-binned path only */
-    if (lay.bytes > LDS_MAX || (c->flags & FH_FORCE_ATOMIC)) return 15;
+    if (!lp.fits || (c->flags & FH_FORCE_ATOMIC)) return 15;
     if (!c->out_ssd) return 16;
   }
 
   if constexpr (U16) {
     /* compact codes exist for the LDS-binned kernel only */
     if ((OPS & B_ARGROW) || c->labels2 || c->emit_codes ||
-        c->ngroups >= (int64_t)CODE_NONE || lay.bytes > LDS_MAX ||
+        c->ngroups >= (int64_t)CODE_NONE || !lp.fits ||
         (c->flags & FH_FORCE_ATOMIC))
       return 12;
   } else if (OPS & B_ARGROW) {
@@ -2609,16 +2313,15 @@ int launch_typed(fh_call* c) {
     return launch_partition<V, L, OPS>(c, pp);
   }
 
-  bool use_lds = lay.bytes <= LDS_MAX;
+  bool use_lds = lp.fits;
   if (c->flags & FH_FORCE_ATOMIC) use_lds = false;
   if (c->flags & FH_FORCE_LDS) {
-    if (lay.bytes > LDS_MAX) return 2; /* cannot honor */
+    if (!lp.fits) return 2; /* cannot honor */
     use_lds = true;
   }
 
   if (use_lds) {
-    int blocks_per_cu = lay.bytes * 2 <= LDS_MAX ? 2 : 1;
-    int nblocks = NUM_CU * blocks_per_cu;
+    int nblocks = NUM_CU * lp.blocks_per_cu;
     /* do not launch more blocks than there is work or scratch for */
     const int64_t block_rows = (int64_t)BLOCK_LDS * (U16 ? U16_ROWS : 1);
     int64_t work_blocks = (c->n + block_rows - 1) / block_rows;
@@ -2665,43 +2368,73 @@ int launch_typed(fh_call* c) {
     return launch_beyond_lds<V, L, OPS>(c);
 }
 
+/* run-time value -> compile-time tag visitors. f is a generic lambda; it
+ * reads the type as `typename decltype(tag)::type` and a constant as
+ * `decltype(tag)::value`. */
+template <typename V> struct TypeTag { using type = V; };
+
+/* value dtype; `bad` is returned for an unknown one */
+template <typename F, typename R>
+R with_vdtype(int vdtype, R bad, F&& f) {
+  switch (vdtype) {
+    case FH_F32: return f(TypeTag<float>{});
+    case FH_F64: return f(TypeTag<double>{});
+    case FH_I64: return f(TypeTag<int64_t>{});
+    case FH_I32: return f(TypeTag<int32_t>{});
+    default: return bad;
+  }
+}
+
+/* op bits of the set; an unknown set is error 4. A launcher refuses the sets
+ * it does not serve with `if constexpr` on the tag, so that no kernel is
+ * instantiated for them. */
+template <typename F>
+int with_ops(int op_set, F&& f) {
+  switch (op_set) {
+#define FH_OPS_CASE(s) \
+  case s: return f(std::integral_constant<int, set_bits(s)>{});
+    FH_OPS_CASE(FH_SET_SUM_COUNT)
+    FH_OPS_CASE(FH_SET_SUM_COUNT_PRESENT)
+    FH_OPS_CASE(FH_SET_COUNT)
+    FH_OPS_CASE(FH_SET_MIN_FULL)
+    FH_OPS_CASE(FH_SET_MIN_COUNT)
+    FH_OPS_CASE(FH_SET_MAX_FULL)
+    FH_OPS_CASE(FH_SET_MAX_COUNT)
+    FH_OPS_CASE(FH_SET_SSD)
+    FH_OPS_CASE(FH_SET_PROD)
+    FH_OPS_CASE(FH_SET_IDXMIN)
+    FH_OPS_CASE(FH_SET_IDXMAX)
+    FH_OPS_CASE(FH_SET_WELFORD)
+    FH_OPS_CASE(FH_SET_ARGMIN_PAIR)
+    FH_OPS_CASE(FH_SET_ARGMAX_PAIR)
+    FH_OPS_CASE(FH_SET_SUMMARY)
+#undef FH_OPS_CASE
+    default: return 4;
+  }
+}
+
+template <typename F>
+int with_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
 template <typename V, typename L>
 int dispatch_ops(fh_call* c) {
-  switch (set_bits(c->op_set)) {
-    case B_SUM | B_CNT: return launch_typed<V, L, B_SUM | B_CNT>(c);
-    case B_SUM | B_CNT | B_PRESENT:
-      return launch_typed<V, L, B_SUM | B_CNT | B_PRESENT>(c);
-    case B_CNT: return launch_typed<V, L, B_CNT>(c);
-    case B_MIN | B_CNT | B_PRESENT | B_NANFLAG:
-      return launch_typed<V, L, B_MIN | B_CNT | B_PRESENT | B_NANFLAG>(c);
-    case B_MIN | B_CNT: return launch_typed<V, L, B_MIN | B_CNT>(c);
-    case B_MAX | B_CNT | B_PRESENT | B_NANFLAG:
-      return launch_typed<V, L, B_MAX | B_CNT | B_PRESENT | B_NANFLAG>(c);
-    case B_MAX | B_CNT: return launch_typed<V, L, B_MAX | B_CNT>(c);
-    case B_SSD: return launch_typed<V, L, B_SSD>(c);
-    case B_PROD | B_CNT | B_PRESENT:
-      return launch_typed<V, L, B_PROD | B_CNT | B_PRESENT>(c);
-    case B_IDXMIN | B_CNT | B_PRESENT:
-      return launch_typed<V, L, B_IDXMIN | B_CNT | B_PRESENT>(c);
-    case B_IDXMAX | B_CNT | B_PRESENT:
-      return launch_typed<V, L, B_IDXMAX | B_CNT | B_PRESENT>(c);
-    case OPS_SUMMARY: return launch_typed<V, L, OPS_SUMMARY>(c);
-    case B_MIN | B_CNT | B_PRESENT | B_NANFLAG | B_ARGROW:
+  return with_ops(c->op_set, [&](auto ops) -> int {
+    constexpr int OPS = decltype(ops)::value;
+    if constexpr ((OPS & B_WELFORD) != 0) {
+      return 4; /* column path only */
+    } else if constexpr ((OPS & B_ARGROW) != 0) {
       if constexpr (std::is_same<L, uint16_t>::value)
         return 12; /* partition path only: no compact-code form */
       else if constexpr (sizeof(V) == 8)
-        return launch_typed<V, L, B_MIN | B_CNT | B_PRESENT | B_NANFLAG | B_ARGROW>(c);
+        return launch_typed<V, L, OPS>(c);
       else
         return 11; /* 4-byte dtypes pack (enc32,row32) keys instead */
-    case B_MAX | B_CNT | B_PRESENT | B_NANFLAG | B_ARGROW:
-      if constexpr (std::is_same<L, uint16_t>::value)
-        return 12;
-      else if constexpr (sizeof(V) == 8)
-        return launch_typed<V, L, B_MAX | B_CNT | B_PRESENT | B_NANFLAG | B_ARGROW>(c);
-      else
-        return 11;
-    default: return 4;
-  }
+    } else {
+      return launch_typed<V, L, OPS>(c);
+    }
+  });
 }
 
 template <typename V>
@@ -2754,7 +2487,6 @@ ColsPlan cols_plan(const fh_call* c) {
 /* init + decode shared with the atomic path, bins sized ngroups*m */
 template <typename V, int OPS>
 int launch_cols(fh_call* c) {
-  using TR = Traits<V>;
   hipStream_t stream = (hipStream_t)c->stream;
   const int64_t nbins = c->ngroups * c->m;
   ColsPlan plan = cols_plan<V>(c);
@@ -2768,109 +2500,49 @@ int launch_cols(fh_call* c) {
     /* identity-fill every chunk's slab sections (bins no segment touches) */
     for (int ch = 0; ch < plan.nchunks; ++ch) {
       char* s = (char*)c->scratch + (int64_t)ch * plan.lay.bytes;
-      if (OPS & (B_SUM | B_SSD | B_WELFORD))
-        FH_CHECK(hipMemsetAsync(s + plan.lay.sum_off, 0, nbins * 8, stream));
-      if (OPS & B_WELFORD)
-        FH_CHECK(hipMemsetAsync(s + plan.lay.sumx_off, 0, nbins * 8, stream));
-      if (OPS & B_PROD) {
-        int fb = (int)((nbins + 255) / 256);
-        if (c->vdtype == FH_F32 || c->vdtype == FH_F64)
-          hipLaunchKernelGGL(k_fill_f64, dim3(fb), dim3(256), 0, stream,
-                             (double*)(s + plan.lay.sum_off), nbins, 1.0);
-        else
-          hipLaunchKernelGGL(k_fill_i64, dim3(fb), dim3(256), 0, stream,
-                             (int64_t*)(s + plan.lay.sum_off), nbins, (int64_t)1);
-        FH_CHECK(hipGetLastError());
-      }
-      if (OPS & B_CNT) FH_CHECK(hipMemsetAsync(s + plan.lay.cnt_off, 0, nbins * 4, stream));
-      if (OPS & B_PRESENT)
-        FH_CHECK(hipMemsetAsync(s + plan.lay.present_off, 0, nbins * 4, stream));
-      if (OPS & B_MIN)
-        FH_CHECK(hipMemsetAsync(s + plan.lay.minmax_off, 0xFF,
-                                nbins * sizeof(typename TR::Enc), stream));
-      if (OPS & B_MAX)
-        FH_CHECK(hipMemsetAsync(s + plan.lay.minmax_off, 0x00,
-                                nbins * sizeof(typename TR::Enc), stream));
-      if (OPS & B_NANFLAG)
-        FH_CHECK(hipMemsetAsync(s + plan.lay.nanflag_off, 0, nbins * 4, stream));
+      FH_TRY((init_bins<V, OPS>(slab_bins(s, plan.lay), nbins, stream)));
     }
   } else {
-    if (OPS & (B_SUM | B_SSD | B_WELFORD))
-      FH_CHECK(hipMemsetAsync(c->out_sum, 0, nbins * 8, stream));
-    if (OPS & B_WELFORD)
-      FH_CHECK(hipMemsetAsync(c->out_min, 0, nbins * 8, stream));
-    if (OPS & B_PROD) {
-      int fb = (int)((nbins + 255) / 256);
-      if (c->vdtype == FH_F32 || c->vdtype == FH_F64)
-        hipLaunchKernelGGL(k_fill_f64, dim3(fb), dim3(256), 0, stream,
-                           (double*)c->out_sum, nbins, 1.0);
-      else
-        hipLaunchKernelGGL(k_fill_i64, dim3(fb), dim3(256), 0, stream,
-                           (int64_t*)c->out_sum, nbins, (int64_t)1);
-      FH_CHECK(hipGetLastError());
-    }
-    if (OPS & B_CNT) FH_CHECK(hipMemsetAsync(c->out_count, 0, nbins * 8, stream));
-    if (OPS & B_PRESENT) FH_CHECK(hipMemsetAsync(c->out_present, 0, nbins * 4, stream));
-    if (OPS & B_MIN)
-      FH_CHECK(hipMemsetAsync(c->out_min, 0xFF, nbins * sizeof(typename TR::Enc), stream));
-    if (OPS & B_MAX)
-      FH_CHECK(hipMemsetAsync(c->out_max, 0x00, nbins * sizeof(typename TR::Enc), stream));
-    if (OPS & B_NANFLAG) FH_CHECK(hipMemsetAsync(c->out_nanflag, 0, nbins * 4, stream));
+    FH_TRY((init_bins<V, OPS>(out_bins(c), nbins, stream)));
   }
 
   dim3 grid((uint32_t)plan.ncolblk, (uint32_t)plan.nchunks);
   const int64_t* offs = aligned_chunks ? (const int64_t*)c->chunk_offsets : nullptr;
-  auto launch = [&](auto kern) -> int {
+  auto launch = [&](auto vc, auto slab, auto skip) -> int {
+    auto kern = k_reduce_cols<V, OPS, decltype(vc)::value, decltype(slab)::value,
+                              decltype(skip)::value>;
     hipLaunchKernelGGL(kern, grid, dim3(COLS_BLOCK), 0, stream,
                        (const V*)c->values, (const int*)c->labels,
                        (const int*)c->perm, c->n, c->m, c->ldm, c->ngroups,
                        c->means, skipnan, plan.chunk_rows, offs,
                        (char*)c->scratch, plan.lay, c->out_sum, c->out_count,
                        c->out_present, c->out_min, c->out_max, c->out_nanflag);
-    return (int)hipGetLastError();
+    FH_CHECK(hipGetLastError());
+    return 0;
   };
-  int rc;
-  const bool sk = skipnan != 0;
-  if constexpr (sizeof(V) == 4) {
-    if (plan.vc == 8) {
-      rc = slab_mode
-               ? launch(sk ? k_reduce_cols<V, OPS, 8, true, true>
-                           : k_reduce_cols<V, OPS, 8, true, false>)
-               : launch(sk ? k_reduce_cols<V, OPS, 8, false, true>
-                           : k_reduce_cols<V, OPS, 8, false, false>);
-      if (rc != 0) return rc + 1000;
-      goto cols_launched;
+  /* columns per thread: 8 (4-byte dtypes only), the dtype's 16-B vector, 1 */
+  auto with_vc = [&](auto f) -> int {
+    if constexpr (sizeof(V) == 4) {
+      if (plan.vc == 8) return f(std::integral_constant<int, 8>{});
     }
-  }
-  if (slab_mode)
-    rc = plan.vc > 1
-             ? launch(sk ? k_reduce_cols<V, OPS, Traits<V>::VEC, true, true>
-                         : k_reduce_cols<V, OPS, Traits<V>::VEC, true, false>)
-             : launch(sk ? k_reduce_cols<V, OPS, 1, true, true>
-                         : k_reduce_cols<V, OPS, 1, true, false>);
-  else
-    rc = plan.vc > 1
-             ? launch(sk ? k_reduce_cols<V, OPS, Traits<V>::VEC, false, true>
-                         : k_reduce_cols<V, OPS, Traits<V>::VEC, false, false>)
-             : launch(sk ? k_reduce_cols<V, OPS, 1, false, true>
-                         : k_reduce_cols<V, OPS, 1, false, false>);
-  if (rc != 0) return rc + 1000;
-cols_launched:;
+    return plan.vc > 1 ? f(std::integral_constant<int, Traits<V>::VEC>{})
+                       : f(std::integral_constant<int, 1>{});
+  };
+  FH_TRY(with_vc([&](auto vc) {
+    return with_bool(slab_mode, [&](auto slab) {
+      return with_bool(skipnan != 0, [&](auto skip) { return launch(vc, slab, skip); });
+    });
+  }));
 
   if (slab_mode) {
     /* fold the chunk partials; k_combine decodes min/max (gridDim.y==1) */
-    int cb = (int)((nbins + 255) / 256);
-    hipLaunchKernelGGL((k_combine<V, OPS>), dim3(cb, 1), dim3(256), 0, stream,
-                       (const char*)c->scratch, plan.nchunks, nbins, plan.lay,
-                       c->out_sum, c->out_count, c->out_present, c->out_min,
-                       c->out_max, c->out_nanflag);
+    hipLaunchKernelGGL((k_combine<V, OPS>), dim3(grid_for(nbins), 1), dim3(256),
+                       0, stream, (const char*)c->scratch, plan.nchunks, nbins,
+                       plan.lay, c->out_sum, c->out_count, c->out_present,
+                       c->out_min, c->out_max, c->out_nanflag);
     FH_CHECK(hipGetLastError());
-  } else if (OPS & (B_MIN | B_MAX)) {
-    int db = (int)((nbins + 255) / 256);
-    hipLaunchKernelGGL((k_decode<V, OPS>), dim3(db), dim3(256), 0, stream,
-                       nbins, c->out_min, c->out_max, c->out_count,
-                       c->out_present);
-    FH_CHECK(hipGetLastError());
+  } else {
+    FH_TRY((launch_decode<V, OPS>(c, nbins, stream)));
   }
   c->path_used = 3;
   return 0;
@@ -2878,23 +2550,13 @@ cols_launched:;
 
 template <typename V>
 int dispatch_cols_ops(fh_call* c) {
-  switch (set_bits(c->op_set)) {
-    case B_SUM | B_CNT: return launch_cols<V, B_SUM | B_CNT>(c);
-    case B_SUM | B_CNT | B_PRESENT:
-      return launch_cols<V, B_SUM | B_CNT | B_PRESENT>(c);
-    case B_CNT: return launch_cols<V, B_CNT>(c);
-    case B_MIN | B_CNT | B_PRESENT | B_NANFLAG:
-      return launch_cols<V, B_MIN | B_CNT | B_PRESENT | B_NANFLAG>(c);
-    case B_MIN | B_CNT: return launch_cols<V, B_MIN | B_CNT>(c);
-    case B_MAX | B_CNT | B_PRESENT | B_NANFLAG:
-      return launch_cols<V, B_MAX | B_CNT | B_PRESENT | B_NANFLAG>(c);
-    case B_MAX | B_CNT: return launch_cols<V, B_MAX | B_CNT>(c);
-    case B_SSD: return launch_cols<V, B_SSD>(c);
-    case B_WELFORD | B_CNT: return launch_cols<V, B_WELFORD | B_CNT>(c);
-    case B_PROD | B_CNT | B_PRESENT:
-      return launch_cols<V, B_PROD | B_CNT | B_PRESENT>(c);
-    default: return 4;
-  }
+  return with_ops(c->op_set, [&](auto ops) -> int {
+    constexpr int OPS = decltype(ops)::value;
+    if constexpr ((OPS & (B_IDXMIN | B_IDXMAX | B_ARGROW | B_MOM2)) != 0)
+      return 4; /* no column form */
+    else
+      return launch_cols<V, OPS>(c);
+  });
 }
 
 }  // namespace
@@ -2936,76 +2598,50 @@ __global__ void k_pack_argkeys(const V* __restrict__ v, int64_t n,
 extern "C" {
 
 int64_t fh_scratch_bytes(const fh_call* c) {
-  int bits = set_bits(c->op_set);
-  int64_t per_block;
-  switch (c->vdtype) {
-    case FH_F32: per_block = bin_layout<float>(bits, c->ngroups, 4).bytes; break;
-    case FH_F64: per_block = bin_layout<double>(bits, c->ngroups, 4).bytes; break;
-    case FH_I64: per_block = bin_layout<int64_t>(bits, c->ngroups, 4).bytes; break;
-    case FH_I32: per_block = bin_layout<int32_t>(bits, c->ngroups, 4).bytes; break;
-    default: return -1;
-  }
-  if (bits & B_MOM2) {
-    /* LDS-binned path or nothing (error 15): never a partition plan */
-    if (c->m > 0 || per_block > LDS_MAX) return 0;
-  }
-  if (c->m > 0) {
-    if (c->chunk_offsets) return 0; /* group-aligned chunks write directly */
-    /* column path: per-chunk slab when the row range is split */
-    ColsPlan p;
-    switch (c->vdtype) {
-      case FH_F32: p = cols_plan<float>(c); break;
-      case FH_F64: p = cols_plan<double>(c); break;
-      case FH_I64: p = cols_plan<int64_t>(c); break;
-      default: p = cols_plan<int32_t>(c); break;
+  return with_vdtype(c->vdtype, (int64_t)-1, [&](auto t) -> int64_t {
+    using V = typename decltype(t)::type;
+    const int bits = set_bits(c->op_set);
+    const LdsPlan lp = lds_plan<V>(bits, c->ngroups);
+    if (bits & B_MOM2) {
+      /* LDS-binned path or nothing (error 15): never a partition plan */
+      if (c->m > 0 || !lp.fits) return 0;
     }
-    return p.nchunks > 1 ? (int64_t)p.nchunks * p.lay.bytes : 0;
-  }
-  if (per_block > LDS_MAX && !(c->flags & FH_FORCE_LDS)) {
-    if (c->flags & FH_FORCE_ATOMIC) return 0;
-    /* partition path wants the pairs buffer + bucket directory */
-    PartPlan p;
-    switch (c->vdtype) {
-      case FH_F32: p = part_plan<float>(c); break;
-      case FH_F64: p = part_plan<double>(c); break;
-      case FH_I64: p = part_plan<int64_t>(c); break;
-      default: p = part_plan<int32_t>(c); break;
+    if (c->m > 0) {
+      if (c->chunk_offsets) return 0; /* group-aligned chunks write directly */
+      /* column path: per-chunk slab when the row range is split */
+      const ColsPlan p = cols_plan<V>(c);
+      return p.nchunks > 1 ? (int64_t)p.nchunks * p.lay.bytes : 0;
     }
-    return p.feasible ? p.bytes : 0;
-  }
-  int blocks_per_cu = per_block * 2 <= LDS_MAX ? 2 : 1;
-  return (int64_t)NUM_CU * blocks_per_cu * per_block;
+    if (!lp.fits && !(c->flags & FH_FORCE_LDS)) {
+      if (c->flags & FH_FORCE_ATOMIC) return 0;
+      /* partition path wants the pairs buffer + bucket directory */
+      const PartPlan p = part_plan<V>(c);
+      return p.feasible ? p.bytes : 0;
+    }
+    return (int64_t)NUM_CU * lp.blocks_per_cu * lp.lay.bytes;
+  });
 }
 
 int fh_query_path(const fh_call* c) {
   if (!c) return -1;
   const int bits = set_bits(c->op_set);
   if (!bits) return -1;
-  int64_t per_block;
-  switch (c->vdtype) {
-    case FH_F32: per_block = bin_layout<float>(bits, c->ngroups, 4).bytes; break;
-    case FH_F64: per_block = bin_layout<double>(bits, c->ngroups, 4).bytes; break;
-    case FH_I64: per_block = bin_layout<int64_t>(bits, c->ngroups, 4).bytes; break;
-    case FH_I32: per_block = bin_layout<int32_t>(bits, c->ngroups, 4).bytes; break;
-    default: return -1;
-  }
-  /* mirrors launch_typed: arg-pair sets never bin in LDS, FORCE_ATOMIC
-   * wins over size, everything else is decided by the bins fitting */
-  if ((bits & B_ARGROW) || (c->flags & FH_FORCE_ATOMIC)) return 0;
-  return per_block <= LDS_MAX ? 1 : 0;
+  return with_vdtype(c->vdtype, -1, [&](auto t) -> int {
+    using V = typename decltype(t)::type;
+    /* arg-pair sets never bin in LDS, FORCE_ATOMIC wins over size,
+     * everything else is decided by the bins fitting */
+    if ((bits & B_ARGROW) || (c->flags & FH_FORCE_ATOMIC)) return 0;
+    return lds_plan<V>(bits, c->ngroups).fits ? 1 : 0;
+  });
 }
 
 int fh_grouped_reduce(fh_call* c) {
   if (!c || !c->values || !c->labels) return 6;
   if (c->labels2 && c->g0 * c->g1 != c->ngroups) return 7;
   if (c->op_set == FH_SET_SSD && !c->means) return 8;
-  switch (c->vdtype) {
-    case FH_F32: return dispatch_label<float>(c);
-    case FH_F64: return dispatch_label<double>(c);
-    case FH_I64: return dispatch_label<int64_t>(c);
-    case FH_I32: return dispatch_label<int32_t>(c);
-    default: return 9;
-  }
+  return with_vdtype(c->vdtype, 9, [&](auto t) {
+    return dispatch_label<typename decltype(t)::type>(c);
+  });
 }
 
 
@@ -3018,13 +2654,9 @@ int fh_grouped_reduce_cols(fh_call* c) {
   if (c->finish) return 14;
   if (c->op_set == FH_SET_SUMMARY) return 15;
   if (c->op_set == FH_SET_SSD && !c->means) return 8;
-  switch (c->vdtype) {
-    case FH_F32: return dispatch_cols_ops<float>(c);
-    case FH_F64: return dispatch_cols_ops<double>(c);
-    case FH_I64: return dispatch_cols_ops<int64_t>(c);
-    case FH_I32: return dispatch_cols_ops<int32_t>(c);
-    default: return 9;
-  }
+  return with_vdtype(c->vdtype, 9, [&](auto t) {
+    return dispatch_cols_ops<typename decltype(t)::type>(c);
+  });
 }
 
 int fh_pack_argkeys(const void* values, int vdtype, int64_t n,
@@ -3032,21 +2664,18 @@ int fh_pack_argkeys(const void* values, int vdtype, int64_t n,
                     void* stream) {
   if (!values || !out || n < 0) return 6;
   if (n + row_offset >= (1LL << 32)) return 10; /* row must fit 32 bits */
-  int64_t wb = (n + 255) / 256;
-  int nblocks = (int)(wb < 8192 ? (wb > 0 ? wb : 1) : 8192);
-  hipStream_t s = (hipStream_t)stream;
-  if (vdtype == FH_F32)
-    hipLaunchKernelGGL(k_pack_argkeys<float>, dim3(nblocks), dim3(256), 0, s,
-                       (const float*)values, n, row_offset, ismax, skipnan,
-                       (int64_t*)out);
-  else if (vdtype == FH_I32)
-    hipLaunchKernelGGL(k_pack_argkeys<int32_t>, dim3(nblocks), dim3(256), 0, s,
-                       (const int32_t*)values, n, row_offset, ismax, skipnan,
-                       (int64_t*)out);
-  else
-    return 9;
-  FH_CHECK(hipGetLastError());
-  return 0;
+  return with_vdtype(vdtype, 9, [&](auto t) -> int {
+    using V = typename decltype(t)::type;
+    if constexpr (sizeof(V) == 4) {
+      hipLaunchKernelGGL(k_pack_argkeys<V>, dim3(capped_grid(n, 256, 8192)),
+                         dim3(256), 0, (hipStream_t)stream, (const V*)values, n,
+                         row_offset, ismax, skipnan, (int64_t*)out);
+      FH_CHECK(hipGetLastError());
+      return 0;
+    } else {
+      return 9; /* 8-byte dtypes take the pair-payload sets instead */
+    }
+  });
 }
 
 const char* fh_error_string(int code) {

@@ -943,3 +943,164 @@ def test_engine_seam_scan_2d():
     from oracle import groupby_scan as oracle_scan
     want = oracle_scan(a, g, func="ffill", expected_groups=np.arange(6))
     np.testing.assert_allclose(out, want, equal_nan=True, rtol=1e-12, atol=1e-12)
+
+
+# ---- host launch layer: partition stages and the column kernel choice ------
+# grouped_partials / grouped_partials_cols called directly, against numpy.
+
+def _np_partials(vals, codes, ngroups):
+    """Partials of the non-skipnan bucket reduce. codes outside [0, ngroups)
+    are dropped rows."""
+    rows = np.flatnonzero((codes >= 0) & (codes < ngroups))
+    g, v = codes[rows], vals[rows]
+    ok = ~np.isnan(v)
+    want = {
+        "count": np.bincount(g[ok], minlength=ngroups),
+        "present": np.bincount(g, minlength=ngroups) > 0,
+        "nanflag": np.bincount(g[~ok], minlength=ngroups) > 0,
+        "sum": np.bincount(g, weights=v.astype(np.float64), minlength=ngroups),
+    }
+    mn = np.full(ngroups, np.inf)
+    np.minimum.at(mn, g[ok], v[ok])
+    # a group of NaN rows only decodes its untouched (all-ones) bin: a NaN
+    mn[want["present"] & (want["count"] == 0)] = np.nan
+    want["min"] = mn
+    idx = np.full(ngroups, np.iinfo(np.int64).max)  # first row holding the min
+    hit = ok & (v == mn[g])
+    np.minimum.at(idx, g[hit], rows[hit])
+    want["idx"] = idx
+    return want
+
+
+def _check_partition_sets(rng, codes, ngroups, **label_kw):
+    """The three op-set families of the issue on one label layout; every
+    call must be served by the bucket-partition path."""
+    from flox_amd import _ffi
+    from flox_amd.aggregate_hip import grouped_partials
+
+    n = codes.size
+    dev = lambda a: torch.tensor(a, device="cuda")  # noqa: E731
+    get = lambda p, k: p[k].cpu().numpy()  # noqa: E731
+
+    v32 = rng.standard_normal(n).astype(np.float32)
+    p = grouped_partials(_ffi.SET_SUM_COUNT, dev(v32), ngroups=ngroups, **label_kw)
+    want = _np_partials(v32, codes, ngroups)
+    assert p["_path"] == 4
+    np.testing.assert_array_equal(get(p, "count"), want["count"])
+    np.testing.assert_allclose(get(p, "sum"), want["sum"], rtol=1e-11)
+
+    v64 = rng.standard_normal(n)
+    v64[rng.random(n) < 0.05] = np.nan
+    p = grouped_partials(_ffi.SET_MIN_FULL, dev(v64), ngroups=ngroups, **label_kw)
+    want = _np_partials(v64, codes, ngroups)
+    assert p["_path"] == 4
+    np.testing.assert_array_equal(get(p, "min"), want["min"])
+    np.testing.assert_array_equal(get(p, "count"), want["count"])
+    np.testing.assert_array_equal(get(p, "present") != 0, want["present"])
+    np.testing.assert_array_equal(get(p, "nanflag") != 0, want["nanflag"])
+
+    vq = np.round(rng.standard_normal(n) * 4) / 4  # quantized: many ties
+    p = grouped_partials(_ffi.SET_ARGMIN_PAIR, dev(vq), ngroups=ngroups, **label_kw)
+    want = _np_partials(vq, codes, ngroups)
+    assert p["_path"] == 4
+    np.testing.assert_array_equal(get(p, "idx"), want["idx"])
+    np.testing.assert_array_equal(get(p, "min"), want["min"])
+    np.testing.assert_array_equal(get(p, "count"), want["count"])
+    np.testing.assert_array_equal(get(p, "present") != 0, want["present"])
+
+
+def _skew(rng, labels, layout):
+    """skewed: 90% of the rows in label 0, past the capacity of bucket 0 (and
+    of super-bucket 0) of 1.25*mean + 8192 rows, so the optimistic scatter
+    overflows and the exact counted path produces the result."""
+    if layout == "skewed":
+        labels[rng.random(labels.size) < 0.9] = 0
+    return labels
+
+
+@pytest.mark.parametrize("layout", ["uniform", "skewed"])
+@pytest.mark.parametrize("ngroups,n", [(20_000, 200_000), (600_000, 300_000)],
+                         ids=["one_level", "two_level"])
+def test_partition_stages_vs_numpy(ngroups, n, layout):
+    """20k groups: 3-5 buckets, one scatter pass. 600k groups: > 64 buckets,
+    two passes. Out-of-range labels (-1, ngroups) must be dropped."""
+    rng = np.random.default_rng(zlib.crc32(f"{ngroups}-{layout}".encode()))
+    labels = _skew(rng, rng.integers(0, ngroups, n), layout)
+    bad = rng.random(n) < 0.01
+    labels[bad] = rng.choice([-1, ngroups], int(bad.sum()))
+    _check_partition_sets(rng, labels, ngroups, labels=torch.tensor(labels, device="cuda"))
+
+
+def test_partition_stages_two_labels_vs_numpy():
+    """Fused 2-D grouping (labels2, grp_shape) through the one-level
+    partition; a row is dropped when either label is out of range."""
+    rng = np.random.default_rng(4060)
+    g0, g1, n = 40, 600, 200_000
+    l0, l1 = rng.integers(0, g0, n), rng.integers(0, g1, n)
+    for lab, g in ((l0, g0), (l1, g1)):
+        bad = rng.random(n) < 0.01
+        lab[bad] = rng.choice([-1, g], int(bad.sum()))
+    valid = (l0 >= 0) & (l0 < g0) & (l1 >= 0) & (l1 < g1)
+    codes = np.where(valid, l0 * g1 + l1, -1)
+    _check_partition_sets(
+        rng, codes, g0 * g1, labels=torch.tensor(l0, device="cuda"),
+        labels2=torch.tensor(l1, device="cuda"), grp_shape=(g0, g1),
+    )
+
+
+@pytest.mark.parametrize("skipnan", [False, True])
+@pytest.mark.parametrize("layout", ["chunked", "slab"])
+@pytest.mark.parametrize("m", [11, 16])  # 1 column per thread / the 8-wide kernel
+def test_column_path_partials_vs_numpy(m, layout, skipnan):
+    """Every (columns per thread, slab, skipnan) kernel choice at f32.
+    chunked: rows of all groups, so the caller hands group-aligned chunks and
+    the kernel writes the outputs directly. slab: all rows in one group, no
+    aligned split exists, so three row chunks go through identity-filled
+    slabs and the combine; the other groups keep the identities."""
+    from flox_amd import _ffi
+    from flox_amd.aggregate_hip import grouped_partials_cols
+
+    rng = np.random.default_rng(zlib.crc32(f"{m}-{layout}".encode()))
+    n, ngroups = 5000, 7
+    codes = rng.integers(0, ngroups, n) if layout == "chunked" else np.full(n, 3)
+    # products of <= 5000 factors near 1 stay finite; NaN in every third column
+    vals = rng.uniform(0.9, 1.1, (n, m)).astype(np.float32)
+    vals[(rng.random((n, m)) < 0.03) & (np.arange(m) % 3 == 0)] = np.nan
+    order = np.argsort(codes, kind="stable")
+    args = (
+        torch.tensor(vals, device="cuda"),
+        torch.tensor(codes[order].astype(np.int32), device="cuda"),
+        torch.tensor(order.astype(np.int32), device="cuda"),
+        ngroups,
+    )
+
+    nan = np.isnan(vals)
+    used = ~nan if skipnan else np.ones_like(nan)
+    count = np.zeros((ngroups, m), np.int64)
+    present = np.zeros((ngroups, m), bool)
+    nanflag = np.zeros((ngroups, m), bool)
+    prod = np.ones((ngroups, m))
+    mn = np.full((ngroups, m), np.inf, np.float32)
+    for g in range(ngroups):
+        r = codes == g
+        if not r.any():
+            continue
+        present[g] = True
+        count[g] = (~nan[r]).sum(0)
+        nanflag[g] = (nan[r] & used[r]).any(0)
+        prod[g] = np.where(used[r], vals[r].astype(np.float64), 1.0).prod(0)
+        mn[g] = np.where(nan[r], np.inf, vals[r]).min(0)
+
+    p = grouped_partials_cols(_ffi.SET_MIN_FULL, *args, skipnan=skipnan)
+    assert p["_path"] == 3
+    np.testing.assert_array_equal(p["min"].cpu().numpy(), mn)
+    np.testing.assert_array_equal(p["count"].cpu().numpy(), count)
+    np.testing.assert_array_equal(p["present"].cpu().numpy() != 0, present)
+    np.testing.assert_array_equal(p["nanflag"].cpu().numpy() != 0, nanflag)
+
+    p = grouped_partials_cols(_ffi.SET_PROD, *args, skipnan=skipnan)
+    assert p["_path"] == 3
+    # <= 5000 roundings of 1.1e-16 in either order: 1.1e-12 apart at most
+    np.testing.assert_allclose(p["sum"].cpu().numpy(), prod, rtol=1e-11, equal_nan=True)
+    np.testing.assert_array_equal(p["count"].cpu().numpy(), count)
+    np.testing.assert_array_equal(p["present"].cpu().numpy() != 0, present)
