@@ -18,7 +18,9 @@ _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libfloxhip
 
 # fh_dtype / fh_ldtype / fh_opset / fh_flags — mirror include/floxhip.h
 F32, F64, I64, I32 = 0, 1, 2, 3
-L_I64, L_I32, L_U16 = 0, 1, 2
+L_I64, L_I32, L_U16, L_P12, L_P14 = 0, 1, 2, 3, 4
+# cached label codes by bits per code (label_cache.py)
+L_CODES = {16: L_U16, 14: L_P14, 12: L_P12}
 SET_SUM_COUNT = 0
 SET_SUM_COUNT_PRESENT = 1
 SET_COUNT = 2
@@ -83,6 +85,7 @@ class FhCall(ctypes.Structure):
         ("target", ctypes.c_void_p),
         ("row_offset", ctypes.c_int64),
         # label-code cache: uint16[n] output of an emitting LDS-path call
+    # (repacked by fh_pack_codes where a narrower width applies)
         ("emit_codes", ctypes.c_void_p),
         # fused finish (fh_finish): result buffer instead of partials
         ("finish", ctypes.c_int),
@@ -129,6 +132,12 @@ def load_library():
         ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
     ]
     lib.fh_pack_argkeys.restype = ctypes.c_int
+    lib.fh_packed_code_bytes.argtypes = [ctypes.c_int64, ctypes.c_int]
+    lib.fh_packed_code_bytes.restype = ctypes.c_int64
+    lib.fh_pack_codes.argtypes = [
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+    ]
+    lib.fh_pack_codes.restype = ctypes.c_int
     lib.fh_error_string.argtypes = [ctypes.c_int]
     lib.fh_error_string.restype = ctypes.c_char_p
     lib.fh_version.argtypes = []
@@ -137,7 +146,7 @@ def load_library():
     lib.fh_query_path.restype = ctypes.c_int
     lib.fh_abi_revision.argtypes = []
     lib.fh_abi_revision.restype = ctypes.c_int
-    if lib.fh_version() != 1 or lib.fh_abi_revision() < 4:
+    if lib.fh_version() != 1 or lib.fh_abi_revision() < 5:
         raise RuntimeError("libfloxhip.so ABI version mismatch")
     _lib = lib
     return lib

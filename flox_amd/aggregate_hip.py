@@ -213,16 +213,18 @@ def grouped_partials(
         and label_cache.CACHE.enabled
         and lib.fh_query_path(ctypes.byref(c)) == 1
     ):
+        width = label_cache.code_width(ngroups, c.n)
         plan = label_cache.CACHE.acquire(
-            label_src, grp_shape if labels2 is not None else ngroups, c.n
+            label_src, grp_shape if labels2 is not None else ngroups, c.n,
+            nbytes=label_cache.code_bytes(c.n, width), width=width,
         )
     if plan is not None and plan.action == label_cache.HIT:
         cur = torch.cuda.current_stream(dev)
         if plan.stream != cur:
             cur.wait_event(plan.event)
-        # a u16 label is the final code, also for two-by
+        # a cached code is the final code, also for two-by
         labels, labels2, grp_shape = plan.codes, None, None
-        c.ldtype = _ffi.L_U16
+        c.ldtype = _ffi.L_CODES[plan.width]
     emit = None
     if plan is not None and plan.action == label_cache.EMIT:
         emit = torch.empty(c.n, dtype=torch.uint16, device=dev)
@@ -234,7 +236,7 @@ def grouped_partials(
     # path, so it also skips the probe and its host sync.
     if (
         labels2 is None
-        and c.ldtype != _ffi.L_U16
+        and c.ldtype in _TORCH_LDTYPE.values()
         and force_path == 0
         and ngroups >= 8192
         and values.numel() >= 1_000_000
@@ -317,16 +319,23 @@ def grouped_partials(
 
     _ffi.check(lib.fh_grouped_reduce(ctypes.byref(c)))
     out["_path"] = c.path_used  # type: ignore[assignment]
+    codes = emit
     if emit is not None:
-        # consumers on other streams wait on this event
         cur = torch.cuda.current_stream(dev)
+        if plan.width != 16:
+            # repack on the same stream; the uint16 stream is released below
+            nb = lib.fh_packed_code_bytes(c.n, plan.width)
+            codes = torch.empty(nb, dtype=torch.uint8, device=dev)
+            _ffi.check(lib.fh_pack_codes(
+                emit.data_ptr(), c.n, plan.width, codes.data_ptr(), c.stream))
+        # consumers on other streams wait on this event
         ev = torch.cuda.Event()
         ev.record(cur)
-        label_cache.CACHE.publish(plan, emit, ev, cur)
+        label_cache.CACHE.publish(plan, codes, ev, cur)
     # keep tensors alive until the stream consumes them (torch caching allocator
     # ties lifetime to the stream via recorded events only for torch ops; we
     # record explicitly)
-    for t in (values, labels, labels2, means, target, scratch, emit):
+    for t in (values, labels, labels2, means, target, scratch, emit, codes):
         _record(t, torch.cuda.current_stream(dev))
     return out
 

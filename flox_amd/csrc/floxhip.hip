@@ -37,6 +37,7 @@
 #include <cstdlib>
 
 #include "../../include/floxhip.h"
+#include "../../include/floxhip_codes.h"
 
 #define FH_CHECK(x)                       \
   do {                                    \
@@ -261,7 +262,8 @@ __host__ __device__ BinLayout bin_layout(int bits, int64_t ngroups, int64_t cnt_
 /* streaming vector load of one Vec. Every input byte of the LDS kernel is
  * read once. NT = nontemporal 16-byte loads: 4.4-5.5 % faster for the
  * int64/int32-label forms (12 B/row), no difference for the u16-code form,
- * which keeps plain loads (profiles/r03_label_cache.md). Vecs narrower
+ * which keeps plain loads (profiles/r03_label_cache.md), 3 % faster for the
+ * packed-code form (profiles/r06_packed_codes.md). Vecs narrower
  * than 16 B are loaded plainly either way. */
 template <typename VT, bool NT>
 __device__ __forceinline__ VT ld_vec(const void* p) {
@@ -283,12 +285,40 @@ constexpr uint32_t CODE_NONE = 0xFFFFu; /* u16 code of a row in no group */
 constexpr int U16_ROWS = 8;  /* rows per lane per iteration, u16-code form */
 constexpr int EMIT_ROWS = 4; /* rows per lane per iteration when emitting */
 
+/* label tags of the packed code forms (include/floxhip_codes.h): `labels`
+ * then points at whole tiles of W-bit codes, 16 rows per lane per tile */
+template <int W> struct PackedCodes { static constexpr int width = W; };
+/* bits per cached code of a label type; 0 = the caller's own labels */
+template <typename L> struct CodeWidth { static constexpr int value = 0; };
+template <> struct CodeWidth<uint16_t> { static constexpr int value = 16; };
+template <int W> struct CodeWidth<PackedCodes<W>> { static constexpr int value = W; };
+
+/* a lane's W/2 dwords of one tile: one load per plane. Nontemporal, like
+ * the values of the packed form: 3 % faster there than plain loads
+ * (profiles/r06_packed_codes.md), unlike in the u16 form. */
+template <int W>
+__device__ __forceinline__ void ld_packed(const char* tile, int lane, uint32_t* cw) {
+  using u32x4 = uint32_t __attribute__((ext_vector_type(4)));
+  using u32x2 = uint32_t __attribute__((ext_vector_type(2)));
+  const u32x4 a = __builtin_nontemporal_load((const u32x4*)(tile + lane * 16));
+  const u32x2 b =
+      __builtin_nontemporal_load((const u32x2*)(tile + FH_PLANE8_OFF + lane * 8));
+  cw[0] = a.x, cw[1] = a.y, cw[2] = a.z, cw[3] = a.w;
+  cw[4] = b.x, cw[5] = b.y;
+  if constexpr (W == 14)
+    cw[6] = __builtin_nontemporal_load(
+        (const uint32_t*)(tile + FH_PLANE4_OFF + lane * 4));
+}
+
 /* ---- kernel 1: LDS-binned grouped reduce --------------------------------
  * L = uint16_t: labels are precomputed final codes (CODE_NONE = no group,
  * labels2 unused); each lane takes U16_ROWS rows per iteration so that every
  * stream is still read with 16-byte loads (one for the codes, 32 or 64 B of
- * values). EMIT: the int64/int32-label run also writes each row's final
- * code to `emit` (EMIT_ROWS rows per lane, one 8-byte store). */
+ * values). L = PackedCodes<W>: the same codes at W = 12 or 14 bits; a wave
+ * takes one 1024-row tile per iteration, each lane W/2 dwords of codes (two
+ * or three coalesced loads) and 16 values in 16-byte loads. EMIT: the
+ * int64/int32-label run also writes each row's final code to `emit`
+ * (EMIT_ROWS rows per lane, one 8-byte store). */
 template <typename V, typename L, int OPS, bool EMIT = false>
 __launch_bounds__(BLOCK_LDS) __global__ void k_reduce_lds(
     const V* __restrict__ values, const L* __restrict__ labels,
@@ -430,6 +460,43 @@ __launch_bounds__(BLOCK_LDS) __global__ void k_reduce_lds(
     }
     for (int64_t i = nvec * U16_ROWS + gtid; i < n; i += stride)
       process(values[i], (int64_t)labels[i], 0, i);
+  } else if constexpr (CodeWidth<L>::value != 0) {
+    /* packed codes: whole tiles, one per wave per iteration. The buffer is
+     * padded to whole tiles, so the code loads need no guard; the values
+     * are read past a full tile only row by row, never past n. */
+    constexpr int W = CodeWidth<L>::value;
+    static_assert(!EMIT, "packed codes are never re-emitted");
+    const int lane = tid & (FH_TILE_LANES - 1);
+    const int64_t nwaves = stride / FH_TILE_LANES;
+    const int64_t nfull = n / FH_TILE_ROWS;
+    const char* codes = reinterpret_cast<const char*>(labels);
+    int64_t tile = gtid / FH_TILE_LANES;
+    for (; tile < nfull; tile += nwaves) {
+      uint32_t cw[W / 2];
+      ld_packed<W>(codes + tile * (FH_TILE_ROWS / 8 * W), lane, cw);
+      Vec<V, VEC> vv[FH_LANE_SLOTS / VEC];
+      const int64_t r0 = tile * FH_TILE_ROWS + lane * 4;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int h = 0; h < 4 / VEC; ++h)
+          vv[j * (4 / VEC) + h] =
+              ld_vec<Vec<V, VEC>, true>(values + r0 + j * 256 + h * VEC);
+#pragma unroll
+      for (int s = 0; s < FH_LANE_SLOTS; ++s)
+        process(vv[s / VEC].v[s % VEC], (int64_t)fh_unpack1<W>(cw, s), 0,
+                r0 + (s >> 2) * 256 + (s & 3));
+    }
+    if (tile == nfull && nfull * FH_TILE_ROWS < n) {
+      /* the last, partial tile: the one wave whose turn it is */
+      uint32_t cw[W / 2];
+      ld_packed<W>(codes + tile * (FH_TILE_ROWS / 8 * W), lane, cw);
+#pragma unroll
+      for (int s = 0; s < FH_LANE_SLOTS; ++s) {
+        const int64_t row = fh_tile_row(tile, lane, s);
+        if (row < n) process(values[row], (int64_t)fh_unpack1<W>(cw, s), 0, row);
+      }
+    }
   } else if constexpr (EMIT) {
     const int64_t nvec = n / EMIT_ROWS;
     for (int64_t i = gtid; i < nvec; i += stride) {
@@ -2232,7 +2299,7 @@ LdsPlan lds_plan(int bits, int64_t ngroups) {
 }
 
 /* everything past the LDS-binned path: sorted-direct, bucket partition,
- * global atomics (never instantiated for uint16 code labels) */
+ * global atomics (never instantiated for cached code labels) */
 template <typename V, typename L, int OPS>
 int launch_beyond_lds(fh_call* c) {
   using TR = Traits<V>;
@@ -2277,7 +2344,8 @@ int launch_typed(fh_call* c) {
   const bool skipnan = (c->flags & FH_SKIPNAN) != 0;
   const LdsPlan lp = lds_plan<V>(OPS, c->ngroups);
   const BinLayout& lay = lp.lay;
-  constexpr bool U16 = std::is_same<L, uint16_t>::value;
+  constexpr int CW = CodeWidth<L>::value; /* cached codes: 16, 14 or 12 bits */
+  constexpr bool CODES = CW != 0;
 
   if (c->finish) {
     /* a finish mode is served by the LDS path's combine only: refuse rather
@@ -2296,10 +2364,11 @@ int launch_typed(fh_call* c) {
     if (!c->out_ssd) return 16;
   }
 
-  if constexpr (U16) {
-    /* compact codes exist for the LDS-binned kernel only */
+  if constexpr (CODES) {
+    /* compact codes exist for the LDS-binned kernel only, and the all-ones
+     * code of the width stays out of range */
     if ((OPS & B_ARGROW) || c->labels2 || c->emit_codes ||
-        c->ngroups >= (int64_t)CODE_NONE || !lp.fits ||
+        c->ngroups >= (int64_t)((1u << CW) - 1u) || !lp.fits ||
         (c->flags & FH_FORCE_ATOMIC))
       return 12;
   } else if (OPS & B_ARGROW) {
@@ -2323,13 +2392,14 @@ int launch_typed(fh_call* c) {
   if (use_lds) {
     int nblocks = NUM_CU * lp.blocks_per_cu;
     /* do not launch more blocks than there is work or scratch for */
-    const int64_t block_rows = (int64_t)BLOCK_LDS * (U16 ? U16_ROWS : 1);
+    const int64_t block_rows =
+        (int64_t)BLOCK_LDS * (CW == 16 ? U16_ROWS : CODES ? FH_LANE_SLOTS : 1);
     int64_t work_blocks = (c->n + block_rows - 1) / block_rows;
     if (work_blocks < nblocks) nblocks = (int)(work_blocks > 0 ? work_blocks : 1);
     if ((int64_t)nblocks * lay.bytes > c->scratch_bytes) return 3;
 
     auto kern = k_reduce_lds<V, L, OPS>;
-    if constexpr (!U16) {
+    if constexpr (!CODES) {
       if (c->emit_codes) {
         if (c->ngroups >= (int64_t)CODE_NONE) return 13;
         kern = k_reduce_lds<V, L, OPS, true>;
@@ -2362,7 +2432,7 @@ int launch_typed(fh_call* c) {
   }
   if constexpr ((OPS & B_MOM2) != 0)
     return 15; /* not reached: refused above */
-  else if constexpr (U16)
+  else if constexpr (CODES)
     return 12; /* not reached: the guard above admits LDS-sized bins only */
   else
     return launch_beyond_lds<V, L, OPS>(c);
@@ -2425,7 +2495,7 @@ int dispatch_ops(fh_call* c) {
     if constexpr ((OPS & B_WELFORD) != 0) {
       return 4; /* column path only */
     } else if constexpr ((OPS & B_ARGROW) != 0) {
-      if constexpr (std::is_same<L, uint16_t>::value)
+      if constexpr (CodeWidth<L>::value != 0)
         return 12; /* partition path only: no compact-code form */
       else if constexpr (sizeof(V) == 8)
         return launch_typed<V, L, OPS>(c);
@@ -2443,6 +2513,8 @@ int dispatch_label(fh_call* c) {
     case FH_L_I64: return dispatch_ops<V, int64_t>(c);
     case FH_L_I32: return dispatch_ops<V, int32_t>(c);
     case FH_L_U16: return dispatch_ops<V, uint16_t>(c);
+    case FH_L_P12: return dispatch_ops<V, PackedCodes<12>>(c);
+    case FH_L_P14: return dispatch_ops<V, PackedCodes<14>>(c);
     default: return 5;
   }
 }
@@ -2595,6 +2667,49 @@ __global__ void k_pack_argkeys(const V* __restrict__ v, int64_t n,
   }
 }
 
+/* rewrite uint16 codes (0xFFFF = no group) into W-bit tiles
+ * (include/floxhip_codes.h): one wave per tile, grid-stride over tiles. Rows
+ * past n take the sentinel, so every slot of the last tile is defined. */
+template <int W>
+__launch_bounds__(256) __global__ void k_pack_codes(
+    const uint16_t* __restrict__ u16, int64_t n, char* __restrict__ out) {
+  constexpr uint32_t NONE = (1u << W) - 1u;
+  const int lane = threadIdx.x & (FH_TILE_LANES - 1);
+  const int64_t nwaves = (int64_t)gridDim.x * blockDim.x / FH_TILE_LANES;
+  const int64_t ntiles = (n + FH_TILE_ROWS - 1) / FH_TILE_ROWS;
+  for (int64_t tile = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / FH_TILE_LANES;
+       tile < ntiles; tile += nwaves) {
+    uint32_t code[FH_LANE_SLOTS];
+    if ((tile + 1) * FH_TILE_ROWS <= n) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const Vec<uint16_t, 4> cv = *reinterpret_cast<const Vec<uint16_t, 4>*>(
+            u16 + fh_tile_row(tile, lane, 4 * j));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) code[4 * j + k] = cv.v[k];
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < FH_LANE_SLOTS; ++s) {
+        const int64_t row = fh_tile_row(tile, lane, s);
+        code[s] = row < n ? (uint32_t)u16[row] : NONE;
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < FH_LANE_SLOTS; ++s)
+      if (code[s] >= NONE) code[s] = NONE;
+    uint32_t cw[W / 2];
+    fh_pack16<W>(code, cw);
+    char* t = out + tile * (FH_TILE_ROWS / 8 * W);
+    *reinterpret_cast<Vec<uint32_t, 4>*>(t + lane * 16) =
+        Vec<uint32_t, 4>{{cw[0], cw[1], cw[2], cw[3]}};
+    *reinterpret_cast<Vec<uint32_t, 2>*>(t + FH_PLANE8_OFF + lane * 8) =
+        Vec<uint32_t, 2>{{cw[4], cw[5]}};
+    if constexpr (W == 14)
+      *reinterpret_cast<uint32_t*>(t + FH_PLANE4_OFF + lane * 4) = cw[6];
+  }
+}
+
 extern "C" {
 
 int64_t fh_scratch_bytes(const fh_call* c) {
@@ -2678,6 +2793,28 @@ int fh_pack_argkeys(const void* values, int vdtype, int64_t n,
   });
 }
 
+int64_t fh_packed_code_bytes(int64_t n, int width) {
+  return fh_packed_bytes(n, width);
+}
+
+int fh_pack_codes(const void* u16, int64_t n, int width, void* out,
+                  void* stream) {
+  if (!u16 || !out || n < 0) return 6;
+  if (width != 12 && width != 14) return 17;
+  if (n == 0) return 0;
+  const int64_t ntiles = (n + FH_TILE_ROWS - 1) / FH_TILE_ROWS;
+  /* 4 waves (tiles) per block */
+  const dim3 grid(capped_grid(ntiles * FH_TILE_LANES, 256, 8192));
+  if (width == 12)
+    hipLaunchKernelGGL(k_pack_codes<12>, grid, dim3(256), 0, (hipStream_t)stream,
+                       (const uint16_t*)u16, n, (char*)out);
+  else
+    hipLaunchKernelGGL(k_pack_codes<14>, grid, dim3(256), 0, (hipStream_t)stream,
+                       (const uint16_t*)u16, n, (char*)out);
+  FH_CHECK(hipGetLastError());
+  return 0;
+}
+
 const char* fh_error_string(int code) {
   switch (code) {
     case 0: return "ok";
@@ -2690,16 +2827,17 @@ const char* fh_error_string(int code) {
     case 8: return "FH_SET_SSD requires means";
     case 9: return "unknown value dtype";
     case 11: return "arg-pair reduction needs the bucket-partition path (8-byte dtype, n < 2^31, ngroups <= 2^24)";
-    case 12: return "uint16 code labels are valid on the LDS-binned path only (single code stream, bins within LDS; see fh_query_path)";
+    case 12: return "code labels (uint16 or packed) are valid on the LDS-binned path only (single code stream, bins within LDS, ngroups below the all-ones code of the width; see fh_query_path)";
     case 13: return "emit_codes needs the LDS-binned path and ngroups < 65535";
     case 14: return "finish mode needs the LDS-binned path, the op set it finishes (mean: SUM_COUNT, sum: SUM_COUNT_PRESENT, count: COUNT) and an f32/f64/i64 result buffer (see fh_query_path)";
     case 15: return "FH_SET_SUMMARY is served by the LDS-binned path only (bins within LDS, no FH_FORCE_ATOMIC, not the column path; see fh_query_path)";
     case 16: return "FH_SET_SUMMARY requires out_ssd";
+    case 17: return "packed code width must be 12 or 14";
     default: return code >= 1000 ? hipGetErrorString((hipError_t)(code - 1000)) : "unknown error";
   }
 }
 
 int fh_version(void) { return 1; }
-int fh_abi_revision(void) { return 4; }
+int fh_abi_revision(void) { return 5; }
 
 }  /* extern "C" */

@@ -4,7 +4,10 @@ The LDS-binned kernel reads 8 B/row of int64 labels only to use them as an
 index below ~4e4. The same ``by`` tensor is typically reduced many times
 (every variable of a Dataset; mean, then var, then count; both passes of
 var), so from the second sighting on the kernel also writes each row's final
-group code as uint16 (2 B/row) and later calls read that stream instead —
+group code as uint16 (2 B/row) and later calls read that stream instead. From
+``PACK_MIN_ROWS`` rows on, the emitted codes are repacked once to the width
+the group count needs (12 bits up to 4094 groups, 14 bits up to 16382:
+1.5 / 1.75 B/row, in whole 1024-row tiles) and the uint16 stream is freed —
 the device-side analogue of xarray's GroupBy factorizing once, and of the
 reference's memoize cache for label-derived work (flox/cache.py).
 
@@ -12,7 +15,7 @@ Policy by sighting of a key:
   1st  record the key only; the call runs exactly the uncached kernel, so a
        one-shot reduction costs nothing extra                       (miss)
   2nd  the ordinary kernel also emits the codes; they are stored    (emit)
-  3rd+ the u16-code kernel runs                                     (hit)
+  3rd+ the code kernel (uint16 or packed) runs                      (hit)
 
 Key: the caller's ``by`` tensor OBJECT(S) — held by weak reference and
 compared by identity, never by address alone (the allocator hands freed
@@ -42,30 +45,56 @@ from collections import OrderedDict
 FIRST, EMIT, HIT = "first", "emit", "hit"
 
 DEFAULT_MAX_ENTRIES = 8
-DEFAULT_MAX_BYTES = 8 << 30  # codes are 2 B/row: 4e9 rows of labels
+DEFAULT_MAX_BYTES = 8 << 30  # codes are at most 2 B/row: 4e9 rows of labels
 
 CODE_BYTES = 2  # uint16
 
+# packed codes (include/floxhip_codes.h). Below PACK_MIN_ROWS rows the uint16
+# form is kept (option label_code_pack_min_rows). Default: measured at 1e7,
+# 3e7 and 1e8 rows, packed was 4 % slower at 3e7 and 4 % faster at 1e8, the
+# smallest size from which it was never slower (profiles/r06_packed_codes.md)
+TILE_ROWS = 1024
+PACK_MIN_ROWS = 100_000_000
+
+
+def code_width(ngroups: int, nrows: int) -> int:
+    """Bits per cached code for a call: 12 or 14 where the group count leaves
+    the all-ones code of that width free and the call is large enough to
+    pack, else 16 (uint16)."""
+    if nrows < PACK_MIN_ROWS:
+        return 16
+    return 12 if ngroups <= 4094 else 14 if ngroups <= 16382 else 16
+
+
+def code_bytes(nrows: int, width: int) -> int:
+    """Bytes of the code stream: whole 1024-row tiles for a packed width
+    (what fh_packed_code_bytes returns), 2 B/row for uint16."""
+    if width == 16:
+        return int(nrows) * CODE_BYTES
+    return -(-int(nrows) // TILE_ROWS) * (TILE_ROWS // 8) * width
+
 
 class _Entry:
-    __slots__ = ("key", "refs", "sig", "codes", "event", "stream", "nbytes")
+    __slots__ = ("key", "refs", "sig", "codes", "event", "stream", "nbytes", "width")
 
-    def __init__(self, key, refs, sig, nbytes):
+    def __init__(self, key, refs, sig, nbytes, width=16):
         self.key = key
         self.refs = refs
         self.sig = sig
-        self.codes = None   # uint16[n] once emitted
-        self.event = None   # recorded after the emitting call
+        self.codes = None   # uint16[n], or the packed tiles, once emitted
+        self.event = None   # recorded after the emitting call (and its packer)
         self.stream = None  # the emitting stream
         self.nbytes = nbytes
+        self.width = width  # bits per code: 16, 14 or 12
 
 
 class Plan:
     """What one call should do: ``action`` is FIRST (run uncached), EMIT
     (run uncached and hand the codes to ``publish``) or HIT (read
-    ``codes``; wait on ``event`` when on another stream than ``stream``)."""
+    ``codes``, ``width`` bits each; wait on ``event`` when on another stream
+    than ``stream``)."""
 
-    __slots__ = ("action", "entry", "codes", "event", "stream")
+    __slots__ = ("action", "entry", "codes", "event", "stream", "width")
 
     def __init__(self, action, entry=None):
         self.action = action
@@ -74,6 +103,7 @@ class Plan:
         self.codes = entry.codes if entry is not None else None
         self.event = entry.event if entry is not None else None
         self.stream = entry.stream if entry is not None else None
+        self.width = entry.width if entry is not None else 16
 
 
 def _signature(srcs):
@@ -124,9 +154,12 @@ class LabelCodeCache:
                 self._drop(key)
 
     # -- the policy ---------------------------------------------------------
-    def acquire(self, srcs, groups, nrows):
+    def acquire(self, srcs, groups, nrows, nbytes=None, width=16):
         """Look the label tensors ``srcs`` (the caller's ``by`` objects) up.
-        ``groups``: ngroups, or (g0, g1) for the fused two-by form. Returns a
+        ``groups``: ngroups, or (g0, g1) for the fused two-by form.
+        ``nbytes``: what the codes of this call would occupy (default: uint16,
+        2 B/row) and ``width`` their bits per code; an entry made for another
+        width (the packing threshold moved) starts over. Returns a
         Plan, or None when the cache is off or the tensors cannot be cached:
         an inference tensor has no version counter, so writes to it could
         not be seen (reading ``_version`` raises) — such a ``by`` runs
@@ -135,14 +168,15 @@ class LabelCodeCache:
             return None
         key = (tuple(id(t) for t in srcs), groups)
         sig = _signature(srcs)
-        nbytes = int(nrows) * CODE_BYTES
+        nbytes = int(nrows) * CODE_BYTES if nbytes is None else int(nbytes)
         with self._lock:
             e = self._entries.get(key)
             if e is not None and (
-                e.sig != sig or any(r() is not t for r, t in zip(e.refs, srcs))
+                e.sig != sig or e.width != width
+                or any(r() is not t for r, t in zip(e.refs, srcs))
             ):
-                # written in place since (``_version``), or a different
-                # tensor that happens to reuse the id: start over
+                # written in place since (``_version``), a different tensor
+                # that happens to reuse the id, or another code width: start over
                 self._drop(key)
                 e = None
             if e is None:
@@ -152,7 +186,7 @@ class LabelCodeCache:
                 refs = tuple(
                     weakref.ref(t, lambda _r, k=key: self._on_dead(k)) for t in srcs
                 )
-                self._entries[key] = _Entry(key, refs, sig, nbytes)
+                self._entries[key] = _Entry(key, refs, sig, nbytes, width)
                 self._evict(keep=key)
                 return Plan(FIRST)
             self._entries.move_to_end(key)

@@ -11,7 +11,11 @@ Supported options:
   label_cache: False turns the label-code cache off (label_cache.py): every
       call reads the caller's labels, as if each were a first sighting.
   label_cache_entries: how many label tensors the cache tracks (LRU).
-  label_cache_bytes: byte budget for the cached uint16 codes (2 B/row).
+  label_cache_bytes: byte budget for the cached codes (2 B/row as uint16;
+      1.5 / 1.75 B/row where they are packed to 12 / 14 bits).
+  label_code_pack_min_rows: row count from which cached codes are packed to
+      the width the group count needs (12 bits up to 4094 groups, 14 bits up
+      to 16382); smaller calls keep the uint16 form (label_cache.py).
   fused_finalize: False makes mean/sum/count return to per-group partials
       finished by torch ops; on (the default) the combine kernel writes the
       finished result where the LDS-binned path serves the call (core.py).
@@ -31,6 +35,7 @@ OPTIONS = {
     "label_cache": None,              # None = on
     "label_cache_entries": None,
     "label_cache_bytes": None,
+    "label_code_pack_min_rows": None,  # None = the measured default
     "fused_finalize": None,           # None = on
     "fused_many": None,               # None = on
 }
@@ -50,6 +55,11 @@ def _apply(name, value):
         old = getattr(label_cache.CACHE, field)
         if value is not None:
             label_cache.CACHE.configure(**{field: value})
+        return (name, old)
+    if name == "label_code_pack_min_rows":
+        old = label_cache.PACK_MIN_ROWS
+        if value is not None:
+            label_cache.PACK_MIN_ROWS = int(value)
         return (name, old)
     if name == "packed_arg_threshold":
         old = core.PACKED_ARG_THRESHOLD
@@ -86,6 +96,8 @@ def _restore(name, old):
 
     if name in _CACHE_FIELDS:
         label_cache.CACHE.configure(**{_CACHE_FIELDS[name]: old})
+    elif name == "label_code_pack_min_rows":
+        label_cache.PACK_MIN_ROWS = old
     elif name == "packed_arg_threshold":
         core.PACKED_ARG_THRESHOLD = old
     elif name == "fused_finalize":

@@ -41,6 +41,14 @@ enum fh_ldtype {
    * the LDS-binned path is taken (fh_query_path() == 1); any other dispatch
    * returns error 12. */
   FH_L_U16 = 2,
+  /* the same codes packed to 12 / 14 bits in 1024-row tiles
+   * (include/floxhip_codes.h; written by fh_pack_codes): `labels` points at
+   * fh_packed_code_bytes(n, W) bytes, the all-ones W-bit value means "in no
+   * group", and ngroups must stay below it (<= 4094 / <= 16382). Same
+   * conditions and error 12 as FH_L_U16. Neither fh_query_path nor
+   * fh_scratch_bytes depends on the label dtype. */
+  FH_L_P12 = 3,
+  FH_L_P14 = 4,
 };
 
 /* Fused op sets: the per-group partials one pass produces.
@@ -237,11 +245,22 @@ int fh_pack_argkeys(const void* values, int vdtype, int64_t n,
                     int64_t row_offset, int ismax, int skipnan, void* out,
                     void* stream);
 
+/* packed label codes (include/floxhip_codes.h): bytes of the packed buffer
+ * for n rows at width 12 or 14 (whole 1024-row tiles; -1 for another
+ * width), and the pass that rewrites uint16[n] codes (the emit_codes output)
+ * into it: 0xFFFF becomes the all-ones W-bit code, as do the padding slots
+ * of the last tile. out: 16-byte aligned. Every code below 0xFFFF must be
+ * below 2^W - 1, which holds when the emitting call had ngroups <= 2^W - 2. */
+int64_t fh_packed_code_bytes(int64_t n, int width);
+int fh_pack_codes(const void* u16, int64_t n, int width, void* out,
+                  void* stream);
+
 const char* fh_error_string(int code);
 int fh_version(void);
 /* append-only revisions of fh_call within one fh_version: 2 added
  * emit_codes, FH_L_U16 and fh_query_path; 3 added the finish fields; 4 added
- * FH_SET_SUMMARY and out_ssd. A caller built against revision R
+ * FH_SET_SUMMARY and out_ssd; 5 added FH_L_P12/FH_L_P14, fh_pack_codes and
+ * fh_packed_code_bytes. A caller built against revision R
  * needs a library with fh_abi_revision() >= R. */
 int fh_abi_revision(void);
 
