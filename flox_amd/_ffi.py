@@ -146,7 +146,7 @@ def load_library():
     lib.fh_query_path.restype = ctypes.c_int
     lib.fh_abi_revision.argtypes = []
     lib.fh_abi_revision.restype = ctypes.c_int
-    if lib.fh_version() != 1 or lib.fh_abi_revision() < 5:
+    if lib.fh_version() != 1 or lib.fh_abi_revision() < 6:
         raise RuntimeError("libfloxhip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -70,7 +70,8 @@ _SET_MEMBERS = {
     _ffi.SET_ARGMIN_PAIR: ("idx", "count", "present", "min", "nanflag"),
     _ffi.SET_ARGMAX_PAIR: ("idx", "count", "present", "max", "nanflag"),
     # one pass for the whole sum/mean/var/std/min/max/count family (LDS path
-    # only; NaN rows touch nothing but nanflag; ssd = f64 M2 about the mean)
+    # or column path; NaN rows touch nothing but nanflag; ssd = f64 M2 about
+    # the mean)
     _ffi.SET_SUMMARY: ("sum", "count", "present", "min", "max", "nanflag", "ssd"),
 }
 
@@ -518,7 +519,10 @@ def grouped_partials_cols(
     """Grouped reduce over the LEADING axis of a 2-D array (n_t, m) with
     column stride 1 (row stride = values2d.stride(0)). codes_sorted/perm:
     int32 tensors from a stable sort of the per-row group codes. Returns
-    per-group partials of shape (ngroups, m)."""
+    per-group partials of shape (ngroups, m). SET_SUMMARY: the seven members
+    grouped_partials documents, for any group count (the column kernel keeps
+    its state in registers); NaN rows only set "nanflag" whatever skipnan
+    says."""
     lib = _ffi.load_library()
     _require_gpu_tensor(values2d, "values")
     assert values2d.ndim == 2 and values2d.stride(1) == 1
@@ -594,6 +598,9 @@ def grouped_partials_cols(
     if "nanflag" in members:
         out["nanflag"] = torch.empty(shape, dtype=torch.int32, device=dev)
         c.out_nanflag = out["nanflag"].data_ptr()
+    if "ssd" in members:
+        out["ssd"] = torch.empty(shape, dtype=torch.float64, device=dev)
+        c.out_ssd = out["ssd"].data_ptr()
 
     nscratch = lib.fh_scratch_bytes(ctypes.byref(c))
     if nscratch < 0:

@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import _ffi, distributed, xrdtypes
-from .aggregate_hip import grouped_partials, grouped_partials_cols, summary_fits
+from .aggregate_hip import _TORCH_VDTYPE, grouped_partials, grouped_partials_cols, summary_fits
 from .aggregations import REDUCTIONS, Aggregation, CustomAggregation
 
 # arg-reductions switch from the two-pass (extremum, then index-match) form to
@@ -236,7 +236,9 @@ class _ManyCall:
     """What the groupby_reduce calls made by one groupby_reduce_many share:
     the factorization, the SET_SUMMARY partials (gathered by the first func
     that needs a kernel pass) and the sort=False group order. `eligible` is
-    decided once, by the first call that reaches the 1-D engine."""
+    decided once, by the first call that reaches the 1-D or the column
+    engine (every call of one groupby_reduce_many has the same leading
+    dims)."""
 
     def __init__(self):
         self.facs = None
@@ -259,6 +261,9 @@ def _from_summary(S, op_set, skipnan):
 
     if op_set == _ffi.SET_SSD:
         return {"sum": nanned(S["ssd"])}
+    if op_set == _ffi.SET_WELFORD:  # the column path's var_chunk triple
+        return {"wssd": nanned(S["ssd"]), "wsum": nanned(S["sum"].to(torch.float64)),
+                "count": S["count"]}
     if op_set == _ffi.SET_SUM_COUNT:
         return {"sum": nanned(S["sum"]), "count": S["count"]}
     if op_set == _ffi.SET_SUM_COUNT_PRESENT:
@@ -926,6 +931,19 @@ class _EngineCols(_Engine):
         )
 
 
+class _EngineColsSummary(_EngineCols):
+    """A fused-set func of an eligible groupby_reduce_many call over leading
+    dims: one SET_SUMMARY column pass serves every pass the call's fused
+    funcs ask for, as _EngineSummary does without leading dims. The column
+    kernel keeps its state in registers, so no group-count limit applies."""
+
+    def run(self, op_set, skipnan, means=None, target=None, finish=None):
+        many = self.p.many
+        if many.partials is None:
+            many.partials = super().run(_ffi.SET_SUMMARY, True)
+        return _from_summary(many.partials, op_set, skipnan)
+
+
 def _fold_lead(p, codes_full, N):
     """Order-dependent reductions with leading dims: fold the lead index
     into the group codes (lead*ngroups + code) and run the 1-D machinery
@@ -959,9 +977,9 @@ def _fold_lead(p, codes_full, N):
 
 
 def _select_engine(p, by):
-    """1-D (summary-served inside an eligible groupby_reduce_many), column,
-    or lead-folded. Fills in the plan's engine fields; the lead fold
-    (_fold_lead) also rewrites its vals, labels and ngroups."""
+    """1-D, column (either summary-served inside an eligible
+    groupby_reduce_many), or lead-folded. Fills in the plan's engine fields;
+    the lead fold (_fold_lead) also rewrites its vals, labels and ngroups."""
     p.label_src, p.row_offset, p.cols = None, p.shard_row_offset, None
     p.many_served = p.lead_folded = False
     many, facs = p.many, p.facs
@@ -1006,7 +1024,16 @@ def _select_engine(p, by):
     scodes64, perm64 = torch.sort(codes_full, stable=True)
     p.cols = (vt, scodes64.to(torch.int32), perm64.to(torch.int32))
     if p.func not in _LEAD_FOLD_FUNCS:
-        return _EngineCols(p)
+        if many is not None:
+            if many.eligible is None:
+                # no summary_fits here: the column kernel has no LDS bins
+                many.eligible = (
+                    not p.dist_on and p.inp.dt_dtype is None
+                    and vt.numel() > 0 and p.ngroups > 0
+                    and vt.dtype in _TORCH_VDTYPE
+                )
+            p.many_served = many.eligible and p.func in FUSED_MANY_FUNCS
+        return _EngineColsSummary(p) if p.many_served else _EngineCols(p)
     # (the column view and the sort above go unused here: kept, since
     # dropping them would change which kernels these calls launch)
     _fold_lead(p, codes_full, N)

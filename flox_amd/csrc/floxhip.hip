@@ -569,15 +569,63 @@ __launch_bounds__(BLOCK_LDS) __global__ void k_reduce_lds(
   }
 }
 
+/* Chan's pairwise merge of two (n, mean, M2) partials into a; an empty side
+ * is skipped, so no 0/0 enters. Unlike the closed form of k_combine's
+ * B_WELFORD branch it never subtracts squared sums, so it stays accurate when
+ * mean^2 >> var. A mean is piv + off, piv a value of the group: the pivots
+ * subtract exactly where the data is clustered (the hard case) and the
+ * offsets are small, so d keeps the precision a single rounded mean loses.
+ * The merged mean stays relative to a's pivot. */
+__device__ __forceinline__ void chan_merge(double na, double& piv_a, double& off_a,
+                                           double& m2_a, double nb, double piv_b,
+                                           double off_b, double m2_b) {
+  if (nb == 0.0) return;
+  if (na == 0.0) {
+    piv_a = piv_b;
+    off_a = off_b;
+    m2_a = m2_b;
+    return;
+  }
+  const double nt = na + nb, d = (piv_b - piv_a) + (off_b - off_a);
+  off_a += d * (nb / nt);
+  m2_a += m2_b + d * d * (na * nb / nt);
+}
+
+/* the column kernel's pivot in the slab's pivot section (one Enc per bin):
+ * x0 is a double in registers, (double)v of a row. 8-byte dtypes store its
+ * bits; 4-byte dtypes store v itself, which (double) restores exactly. */
+template <typename V>
+__device__ __forceinline__ typename Traits<V>::Enc cols_piv_pack(double x0) {
+  if constexpr (sizeof(V) == 8) {
+    return (uint64_t)__double_as_longlong(x0);
+  } else if constexpr (std::is_same<V, float>::value) {
+    return __float_as_uint((float)x0);
+  } else {
+    return (uint32_t)(int32_t)x0;
+  }
+}
+template <typename V>
+__device__ __forceinline__ double cols_piv_unpack(typename Traits<V>::Enc e) {
+  if constexpr (sizeof(V) == 8) {
+    return __longlong_as_double((long long)e);
+  } else if constexpr (std::is_same<V, float>::value) {
+    return (double)__uint_as_float(e);
+  } else {
+    return (double)(int32_t)e;
+  }
+}
+
 /* ---- kernel 2: combine per-chunk slabs (column path) ---------------------
  * one thread per bin folds every chunk's partial and writes the final bin
  * (min/max decoded inline). The LDS-binned path folds its per-block slab
- * with k_combine_tree below. */
+ * with k_combine_tree below. The summary set folds the chunks' (n, x0 + off,
+ * M2) triples in chunk order with chan_merge, as k_combine_tree does. */
 template <typename V, int OPS>
 __global__ void k_combine(const char* __restrict__ slab, int nblocks,
                           int64_t ngroups, BinLayout lay, void* out_sum,
                           int64_t* out_count, uint32_t* out_present,
-                          void* out_min, void* out_max, uint32_t* out_nanflag) {
+                          void* out_min, void* out_max, uint32_t* out_nanflag,
+                          double* out_ssd) {
   using TR = Traits<V>;
   using Acc = typename TR::Acc;
   using SumT = typename std::conditional<
@@ -587,6 +635,36 @@ __global__ void k_combine(const char* __restrict__ slab, int nblocks,
   constexpr bool IS_PROD = (OPS & B_PROD) != 0;
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= ngroups) return;
+  if constexpr ((OPS & B_MOM2) != 0) {
+    Acc s = 0;
+    int64_t c = 0;
+    uint32_t nf = 0;
+    Enc mn = (Enc)~(Enc)0, mx = (Enc)0;
+    double piv = 0.0, off = 0.0, m2 = 0.0;
+    for (int b = 0; b < nblocks; ++b) {
+      const char* blk = slab + (int64_t)b * lay.bytes;
+      const uint32_t nb = ((const uint32_t*)(blk + lay.cnt_off))[g];
+      chan_merge((double)c, piv, off, m2, (double)nb,
+                 cols_piv_unpack<V>(((const Enc*)(blk + lay.pivot_off))[g]),
+                 ((const double*)(blk + lay.s1_off))[g],
+                 ((const double*)(blk + lay.s2_off))[g]);
+      s += ((const Acc*)(blk + lay.sum_off))[g];
+      c += (int64_t)nb;
+      const Enc lo = ((const Enc*)(blk + lay.minmax_off))[g];
+      const Enc hi = ((const Enc*)(blk + lay.max_off))[g];
+      mn = lo < mn ? lo : mn;
+      mx = hi > mx ? hi : mx;
+      nf |= ((const uint32_t*)(blk + lay.nanflag_off))[g];
+    }
+    ((Acc*)out_sum)[g] = s;
+    out_count[g] = c;
+    out_nanflag[g] = nf;
+    out_present[g] = (c != 0 || nf != 0) ? 1u : 0u; /* any row seen */
+    ((V*)out_min)[g] = c != 0 ? TR::dec(mn) : TR::pos_inf();
+    ((V*)out_max)[g] = c != 0 ? TR::dec(mx) : (V)-TR::pos_inf();
+    out_ssd[g] = m2 > 0.0 ? m2 : 0.0;
+    return;
+  }
   SumT s = IS_PROD ? (SumT)1 : (SumT)0;
   if (OPS & B_IDXMIN) s = (SumT)INT64_MAX;
   if (OPS & B_IDXMAX) s = (SumT)(-1);
@@ -685,28 +763,6 @@ __device__ __forceinline__ void store_finished(const FinishArgs& fa, int64_t g,
     case FH_F64: ((double*)fa.result)[g] = masked ? fa.fill : (double)val; break;
     default: ((int64_t*)fa.result)[g] = masked ? (int64_t)fa.fill : (int64_t)val; break;
   }
-}
-
-/* Chan's pairwise merge of two (n, mean, M2) partials into a; an empty side
- * is skipped, so no 0/0 enters. Unlike the closed form k_combine uses for the
- * column path it never subtracts squared sums, so it stays accurate when
- * mean^2 >> var. A mean is piv + off, piv a value of the group: the pivots
- * subtract exactly where the data is clustered (the hard case) and the
- * offsets are small, so d keeps the precision a single rounded mean loses.
- * The merged mean stays relative to a's pivot. */
-__device__ __forceinline__ void chan_merge(double na, double& piv_a, double& off_a,
-                                           double& m2_a, double nb, double piv_b,
-                                           double off_b, double m2_b) {
-  if (nb == 0.0) return;
-  if (na == 0.0) {
-    piv_a = piv_b;
-    off_a = off_b;
-    m2_a = m2_b;
-    return;
-  }
-  const double nt = na + nb, d = (piv_b - piv_a) + (off_b - off_a);
-  off_a += d * (nb / nt);
-  m2_a += m2_b + d * d * (na * nb / nt);
 }
 
 template <typename V, int OPS, int FIN>
@@ -960,7 +1016,7 @@ __launch_bounds__(COLS_BLOCK) __global__ void k_reduce_cols(
     int64_t chunk_rows, const int64_t* __restrict__ chunk_offs,
     char* __restrict__ slab, BinLayout lay,
     void* out_sum, int64_t* out_count, uint32_t* out_present, void* out_min,
-    void* out_max, uint32_t* out_nanflag) {
+    void* out_max, uint32_t* out_nanflag, double* out_ssd) {
   using TR = Traits<V>;
   using Acc = typename TR::Acc;
   using SumT = typename std::conditional<
@@ -968,6 +1024,12 @@ __launch_bounds__(COLS_BLOCK) __global__ void k_reduce_cols(
       typename std::conditional<(OPS & (B_IDXMIN | B_IDXMAX)) != 0, int64_t, Acc>::type>::type;
   using Enc = typename TR::Enc;
   constexpr bool IS_PROD = (OPS & B_PROD) != 0;
+  /* the summary set: acc is the direct sum, and per column the pivoted
+   * moments ride along: x0 = the segment's first non-NaN value (cnt == 0
+   * until it arrives), s1 = sum(x - x0), s2 = sum((x - x0)^2). A NaN row sets
+   * nanflag and nothing else, so SKIP is always true here. */
+  constexpr bool MOM2 = (OPS & B_MOM2) != 0;
+  static_assert(!MOM2 || (OPS == OPS_SUMMARY && SKIP), "summary set: skipping form only");
 
   __shared__ int s_code[COLS_TTILE];
   __shared__ int s_perm[COLS_TTILE];
@@ -994,6 +1056,7 @@ __launch_bounds__(COLS_BLOCK) __global__ void k_reduce_cols(
   /* shifted-variance state: s1 = sum(x - x0), acc holds s2 = sum((x-x0)^2) */
   double w_s1[VC], w_x0[VC];
   uint32_t w_have[VC];
+  double q_x0[MOM2 ? VC : 1], q_s1[MOM2 ? VC : 1], q_s2[MOM2 ? VC : 1];
   int cur_g = -1;
 
   auto reset = [&]() {
@@ -1009,6 +1072,11 @@ __launch_bounds__(COLS_BLOCK) __global__ void k_reduce_cols(
         w_x0[k] = 0.0;
         w_have[k] = 0;
       }
+      if constexpr (MOM2) {
+        q_x0[k] = 0.0;
+        q_s1[k] = 0.0;
+        q_s2[k] = 0.0;
+      }
     }
   };
   reset();
@@ -1019,6 +1087,36 @@ __launch_bounds__(COLS_BLOCK) __global__ void k_reduce_cols(
     for (int k = 0; k < VC; ++k) {
       if (c0 + k >= m) break;
       const int64_t o = (int64_t)g * m + c0 + k;
+      if constexpr (MOM2) {
+        /* M2 about the segment mean; the slab keeps the mean in its two
+         * parts, x0 and s1/n, so that the merge subtracts pivots exactly */
+        double off = 0.0, m2 = 0.0;
+        if (cnt[k]) {
+          const double dn = (double)cnt[k];
+          off = q_s1[k] / dn;
+          m2 = q_s2[k] - q_s1[k] * q_s1[k] / dn;
+          if (m2 < 0.0) m2 = 0.0; /* rounding only: M2 >= 0 by Cauchy-Schwarz */
+        }
+        if (SLAB) {
+          ((Acc*)(my_slab + lay.sum_off))[o] = acc[k];
+          ((uint32_t*)(my_slab + lay.cnt_off))[o] = cnt[k];
+          ((Enc*)(my_slab + lay.minmax_off))[o] = mn[k];
+          ((Enc*)(my_slab + lay.max_off))[o] = mx[k];
+          ((uint32_t*)(my_slab + lay.nanflag_off))[o] = nanflag[k];
+          ((Enc*)(my_slab + lay.pivot_off))[o] = cols_piv_pack<V>(q_x0[k]);
+          ((double*)(my_slab + lay.s1_off))[o] = off;
+          ((double*)(my_slab + lay.s2_off))[o] = m2;
+        } else {
+          ((Acc*)out_sum)[o] = acc[k];
+          out_count[o] = (int64_t)cnt[k];
+          ((Enc*)out_min)[o] = mn[k]; /* decoded by k_decode */
+          ((Enc*)out_max)[o] = mx[k];
+          out_nanflag[o] = nanflag[k];
+          out_present[o] = (cnt[k] != 0 || nanflag[k] != 0) ? 1u : 0u;
+          out_ssd[o] = m2;
+        }
+        continue;
+      }
       if (IS_WEL) {
         /* convert shifted sums to the var_chunk triple: sum = s1 + n*x0,
          * ssd = s2 - s1^2/n (the mean-shifted form) */
@@ -1059,6 +1157,23 @@ __launch_bounds__(COLS_BLOCK) __global__ void k_reduce_cols(
     /* SKIP is compile-time (skipnan-templated variants): the skip branch
      * and the count select drop out of the per-element stream */
     const bool vnan = TR::isnan_(v);
+    if constexpr (MOM2) {
+      if (vnan) {
+        nanflag[k] = 1u;
+        return;
+      }
+      const double x = (double)v;
+      if (cnt[k] == 0) q_x0[k] = x;
+      const double d = x - q_x0[k];
+      q_s1[k] += d;
+      q_s2[k] += d * d;
+      acc[k] += (Acc)v;
+      cnt[k] += 1u;
+      const Enc e = TR::enc(v);
+      mn[k] = e < mn[k] ? e : mn[k];
+      mx[k] = e > mx[k] ? e : mx[k];
+      return;
+    }
     if constexpr (SKIP) {
       if (vnan) return;
     }
@@ -1896,20 +2011,25 @@ inline hipError_t fill_bins(void* p, int64_t n, double v, hipStream_t stream) {
 struct BinPtrs {
   void *sum, *cnt, *present, *min, *max, *nanflag, *sumx;
   int cnt_bytes;
+  /* B_MOM2: the M2 bins (out_ssd, or a chunk's s2 section). `present` is
+   * then null in a slab, which has no such section for the set. */
+  void* ssd;
 };
 
 inline BinPtrs out_bins(const fh_call* c) {
   /* B_WELFORD's sum-of-x rides the out_min slot */
   return {c->out_sum, c->out_count, c->out_present, c->out_min,
-          c->out_max, c->out_nanflag, c->out_min, 8};
+          c->out_max, c->out_nanflag, c->out_min, 8, c->out_ssd};
 }
 
 inline BinPtrs slab_bins(char* s, const BinLayout& lay) {
   /* sections a set lacks (offset -1) are never touched; min and max share
-   * minmax_off (no slab set carries both) */
-  return {s + lay.sum_off, s + lay.cnt_off, s + lay.present_off,
-          s + lay.minmax_off, s + lay.minmax_off, s + lay.nanflag_off,
-          s + lay.sumx_off, 4};
+   * minmax_off except in the summary set, whose max has max_off */
+  const bool mom2 = lay.max_off >= 0;
+  return {s + lay.sum_off, s + lay.cnt_off,
+          mom2 ? nullptr : s + lay.present_off, s + lay.minmax_off,
+          s + (mom2 ? lay.max_off : lay.minmax_off), s + lay.nanflag_off,
+          s + lay.sumx_off, 4, mom2 ? s + lay.s2_off : nullptr};
 }
 
 /* identity-fill every section of OPS: min bins 0xFF.., max bins 0x00.. (the
@@ -1931,6 +2051,12 @@ int init_bins(const BinPtrs& b, int64_t nbins, hipStream_t stream) {
   if (OPS & B_MAX)
     FH_CHECK(hipMemsetAsync(b.max, 0x00, nbins * sizeof(typename TR::Enc), stream));
   if (OPS & B_NANFLAG) FH_CHECK(hipMemsetAsync(b.nanflag, 0, nbins * 4, stream));
+  if constexpr ((OPS & B_MOM2) != 0) {
+    /* bins no segment touches: M2 0, and "no row seen". A slab's pivot and
+     * offset sections stay unwritten: the merge skips a side with count 0. */
+    FH_CHECK(hipMemsetAsync(b.ssd, 0, nbins * 8, stream));
+    if (b.present) FH_CHECK(hipMemsetAsync(b.present, 0, nbins * 4, stream));
+  }
   return 0;
 }
 
@@ -2523,6 +2649,19 @@ int dispatch_label(fh_call* c) {
 /* launch geometry for the column path: vector width per thread, column
  * blocks, and how many row chunks to split into so the chip is filled
  * (~2048 workgroups) when the column count alone is too small */
+/* columns per thread of the summary set, by value size. Its per-column state
+ * is 12-14 VGPRs against the 3-5 of every other set, so it does not simply
+ * take their widths (profiles/r07_cols_summary.md has the resource report and
+ * the measured A/B between the candidates). */
+#ifndef FH_COLS_SUMMARY_VC4B
+#define FH_COLS_SUMMARY_VC4B 4
+#endif
+#ifndef FH_COLS_SUMMARY_VC8B
+#define FH_COLS_SUMMARY_VC8B 2
+#endif
+template <typename V>
+constexpr int COLS_SUMMARY_VC = sizeof(V) == 4 ? FH_COLS_SUMMARY_VC4B : FH_COLS_SUMMARY_VC8B;
+
 struct ColsPlan {
   int vc;
   int64_t ncolblk;
@@ -2541,6 +2680,10 @@ ColsPlan cols_plan(const fh_call* c) {
       ((uintptr_t)c->values % 32) == 0)
     p.vc = 8;
   if (c->ldm % p.vc != 0 || ((uintptr_t)c->values % 16) != 0) p.vc = 1;
+  if (set_bits(c->op_set) & B_MOM2) {
+    /* narrower loads are aligned wherever wider ones are */
+    p.vc = p.vc >= COLS_SUMMARY_VC<V> ? COLS_SUMMARY_VC<V> : 1;
+  }
   p.ncolblk = (c->m + (int64_t)COLS_BLOCK * p.vc - 1) / ((int64_t)COLS_BLOCK * p.vc);
   if (p.ncolblk == 0) p.ncolblk = 1;
   int want = (int)((2048 + p.ncolblk - 1) / p.ncolblk);
@@ -2588,21 +2731,31 @@ int launch_cols(fh_call* c) {
                        (const int*)c->perm, c->n, c->m, c->ldm, c->ngroups,
                        c->means, skipnan, plan.chunk_rows, offs,
                        (char*)c->scratch, plan.lay, c->out_sum, c->out_count,
-                       c->out_present, c->out_min, c->out_max, c->out_nanflag);
+                       c->out_present, c->out_min, c->out_max, c->out_nanflag,
+                       (double*)c->out_ssd);
     FH_CHECK(hipGetLastError());
     return 0;
   };
   /* columns per thread: 8 (4-byte dtypes only), the dtype's 16-B vector, 1 */
   auto with_vc = [&](auto f) -> int {
-    if constexpr (sizeof(V) == 4) {
-      if (plan.vc == 8) return f(std::integral_constant<int, 8>{});
+    if constexpr ((OPS & B_MOM2) != 0) {
+      return plan.vc > 1 ? f(std::integral_constant<int, COLS_SUMMARY_VC<V>>{})
+                         : f(std::integral_constant<int, 1>{});
+    } else {
+      if constexpr (sizeof(V) == 4) {
+        if (plan.vc == 8) return f(std::integral_constant<int, 8>{});
+      }
+      return plan.vc > 1 ? f(std::integral_constant<int, Traits<V>::VEC>{})
+                         : f(std::integral_constant<int, 1>{});
     }
-    return plan.vc > 1 ? f(std::integral_constant<int, Traits<V>::VEC>{})
-                       : f(std::integral_constant<int, 1>{});
   };
   FH_TRY(with_vc([&](auto vc) {
     return with_bool(slab_mode, [&](auto slab) {
-      return with_bool(skipnan != 0, [&](auto skip) { return launch(vc, slab, skip); });
+      /* the summary set has the skipping form only: NaN rows mark nanflag */
+      if constexpr ((OPS & B_MOM2) != 0)
+        return launch(vc, slab, std::true_type{});
+      else
+        return with_bool(skipnan != 0, [&](auto skip) { return launch(vc, slab, skip); });
     });
   }));
 
@@ -2611,7 +2764,8 @@ int launch_cols(fh_call* c) {
     hipLaunchKernelGGL((k_combine<V, OPS>), dim3(grid_for(nbins), 1), dim3(256),
                        0, stream, (const char*)c->scratch, plan.nchunks, nbins,
                        plan.lay, c->out_sum, c->out_count, c->out_present,
-                       c->out_min, c->out_max, c->out_nanflag);
+                       c->out_min, c->out_max, c->out_nanflag,
+                       (double*)c->out_ssd);
     FH_CHECK(hipGetLastError());
   } else {
     FH_TRY((launch_decode<V, OPS>(c, nbins, stream)));
@@ -2624,10 +2778,17 @@ template <typename V>
 int dispatch_cols_ops(fh_call* c) {
   return with_ops(c->op_set, [&](auto ops) -> int {
     constexpr int OPS = decltype(ops)::value;
-    if constexpr ((OPS & (B_IDXMIN | B_IDXMAX | B_ARGROW | B_MOM2)) != 0)
+    if constexpr ((OPS & (B_IDXMIN | B_IDXMAX | B_ARGROW)) != 0) {
       return 4; /* no column form */
-    else
+    } else if constexpr ((OPS & B_MOM2) != 0) {
+      if (!c->out_ssd) return 16;
+      if (!c->out_sum || !c->out_count || !c->out_present || !c->out_min ||
+          !c->out_max || !c->out_nanflag)
+        return 6;
       return launch_cols<V, OPS>(c);
+    } else {
+      return launch_cols<V, OPS>(c);
+    }
   });
 }
 
@@ -2718,8 +2879,11 @@ int64_t fh_scratch_bytes(const fh_call* c) {
     const int bits = set_bits(c->op_set);
     const LdsPlan lp = lds_plan<V>(bits, c->ngroups);
     if (bits & B_MOM2) {
-      /* LDS-binned path or nothing (error 15): never a partition plan */
-      if (c->m > 0 || !lp.fits) return 0;
+      /* a call that would be refused needs no scratch. 1-D: LDS-binned
+       * path or nothing (error 15), never a partition plan. Column form
+       * (m > 0): error 16 without out_ssd; otherwise its slab is sized
+       * below like any other set's */
+      if (c->m > 0 ? !c->out_ssd : !lp.fits) return 0;
     }
     if (c->m > 0) {
       if (c->chunk_offsets) return 0; /* group-aligned chunks write directly */
@@ -2767,7 +2931,6 @@ int fh_grouped_reduce_cols(fh_call* c) {
    * Outputs are (ngroups, m) group-major. */
   if (!c || !c->values || !c->labels || !c->perm) return 6;
   if (c->finish) return 14;
-  if (c->op_set == FH_SET_SUMMARY) return 15;
   if (c->op_set == FH_SET_SSD && !c->means) return 8;
   return with_vdtype(c->vdtype, 9, [&](auto t) {
     return dispatch_cols_ops<typename decltype(t)::type>(c);
@@ -2822,7 +2985,7 @@ const char* fh_error_string(int code) {
     case 3: return "scratch buffer too small (call fh_scratch_bytes)";
     case 4: return "unknown op_set";
     case 5: return "unknown label dtype";
-    case 6: return "null values/labels pointer";
+    case 6: return "null values/labels pointer, or a missing output buffer of FH_SET_SUMMARY";
     case 7: return "labels2 given but g0*g1 != ngroups";
     case 8: return "FH_SET_SSD requires means";
     case 9: return "unknown value dtype";
@@ -2830,7 +2993,7 @@ const char* fh_error_string(int code) {
     case 12: return "code labels (uint16 or packed) are valid on the LDS-binned path only (single code stream, bins within LDS, ngroups below the all-ones code of the width; see fh_query_path)";
     case 13: return "emit_codes needs the LDS-binned path and ngroups < 65535";
     case 14: return "finish mode needs the LDS-binned path, the op set it finishes (mean: SUM_COUNT, sum: SUM_COUNT_PRESENT, count: COUNT) and an f32/f64/i64 result buffer (see fh_query_path)";
-    case 15: return "FH_SET_SUMMARY is served by the LDS-binned path only (bins within LDS, no FH_FORCE_ATOMIC, not the column path; see fh_query_path)";
+    case 15: return "fh_grouped_reduce serves FH_SET_SUMMARY on the LDS-binned path only (bins within LDS, no FH_FORCE_ATOMIC; see fh_query_path)";
     case 16: return "FH_SET_SUMMARY requires out_ssd";
     case 17: return "packed code width must be 12 or 14";
     default: return code >= 1000 ? hipGetErrorString((hipError_t)(code - 1000)) : "unknown error";
@@ -2838,6 +3001,6 @@ const char* fh_error_string(int code) {
 }
 
 int fh_version(void) { return 1; }
-int fh_abi_revision(void) { return 5; }
+int fh_abi_revision(void) { return 6; }
 
 }  /* extern "C" */

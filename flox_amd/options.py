@@ -21,7 +21,9 @@ Supported options:
       finished result where the LDS-binned path serves the call (core.py).
   fused_many: False makes groupby_reduce_many run every func through its own
       groupby_reduce passes; on (the default) the sum/mean/var/std/min/max/
-      count family shares one SET_SUMMARY pass on eligible calls (core.py).
+      count family shares one SET_SUMMARY pass on eligible calls: on the
+      LDS-binned path without leading dims, on the column path (any group
+      count) with them (core.py).
 """
 
 from __future__ import annotations

@@ -97,7 +97,8 @@ enum fh_opset {
   FH_SET_ARGMIN_PAIR = 12,
   FH_SET_ARGMAX_PAIR = 13,
   /* every partial the sum/mean/var/std/min/max/count family (and its nan*
-   * twins) needs, from ONE pass on the LDS-binned path. NaN rows contribute
+   * twins) needs, from ONE pass on the LDS-binned path or on the column
+   * path. NaN rows contribute
    * nothing to any member but nanflag (FH_SKIPNAN is implied), so the
    * non-skipping functions are derived by the caller: NaN where nanflag is
    * set. Outputs: out_sum (f64 / i64, as FH_SET_SUM_COUNT), out_count (non-NaN
@@ -111,9 +112,14 @@ enum fh_opset {
    * two parts so that differences of means stay exact, and the combine folds
    * the triples in a fixed order with Chan's pairwise merge
    * M2 = M2_a + M2_b + d^2 n_a n_b / (n_a + n_b), d = mean_b - mean_a.
-   * Served by the LDS-binned path only (fh_query_path() == 1): any other
-   * dispatch of fh_grouped_reduce returns error 15 without launching, and
-   * fh_grouped_reduce_cols rejects the set. No finish mode applies
+   * fh_grouped_reduce serves the set on the LDS-binned path only
+   * (fh_query_path() == 1): any other dispatch returns error 15 without
+   * launching. fh_grouped_reduce_cols serves it at any group count, outputs
+   * (ngroups, m): each thread keeps the same state per column in registers
+   * (x0 = the segment's first non-NaN value) and writes final bins, or, where
+   * the row range is split without group alignment, per-chunk triples that
+   * the combine folds in chunk order with the same merge. Error 16 without
+   * out_ssd, 6 without another member's buffer. No finish mode applies
    * (error 14). */
   FH_SET_SUMMARY = 14,
 };
@@ -219,7 +225,9 @@ typedef struct fh_call {
   void* out_ssd;
 } fh_call;
 
-/* scratch requirement for this call (0 when the global-atomic path is used) */
+/* scratch requirement for this call (0 when the global-atomic path is used,
+ * and for an FH_SET_SUMMARY call that would be refused: off the LDS-binned
+ * path in 1-D, without out_ssd on the column path) */
 int64_t fh_scratch_bytes(const fh_call* c);
 
 /* which path fh_grouped_reduce would take for this call, without running
@@ -260,7 +268,8 @@ int fh_version(void);
 /* append-only revisions of fh_call within one fh_version: 2 added
  * emit_codes, FH_L_U16 and fh_query_path; 3 added the finish fields; 4 added
  * FH_SET_SUMMARY and out_ssd; 5 added FH_L_P12/FH_L_P14, fh_pack_codes and
- * fh_packed_code_bytes. A caller built against revision R
+ * fh_packed_code_bytes; 6 added FH_SET_SUMMARY to fh_grouped_reduce_cols. A
+ * caller built against revision R
  * needs a library with fh_abi_revision() >= R. */
 int fh_abi_revision(void);
 

@@ -9,6 +9,11 @@ with the label-code cache warm (same `by` tensor, codes held) and cold
 (k_reduce_lds + k_combine_tree) on its own with its bytes per row and share
 of the measured 6.29 TB/s copy ceiling. Prints one JSON line per workload.
 
+The column workloads (COLS_WORKLOADS: time-major data grouped over axis 0
+through a permute view, so the leading dims become the column path's columns)
+are timed the same three ways, cache state aside (the column path has no
+label-code cache), plus the fused SET_SUMMARY column pass on its own.
+
 --root DIR imports flox_amd from DIR instead of this checkout (a build of
 another commit, which may lack groupby_reduce_many: those forms are then
 reported as null). Not part of the test suite; bench.py is untouched.
@@ -31,6 +36,100 @@ WORKLOADS = {
 }
 
 
+# time-major (n_t, *lead) arrays grouped over axis 0: BASELINE config 4's
+# hour-of-day climatology, and an f64 shape with NaNs and 12 groups
+COLS_WORKLOADS = {
+    "cols_f32_8760x720x1440_24g": dict(shape=(8760, 720, 1440), dtype="float32", groups=24, nan=0.0),
+    "cols_f64_2000x512x512_12g_nan5": dict(shape=(2000, 512, 512), dtype="float64", groups=12, nan=0.05),
+}
+
+
+def bench_cols(args, torch, flox_amd, name, w):
+    from flox_amd import _ffi, aggregate_hip
+
+    many = getattr(flox_amd, "groupby_reduce_many", None)
+    n_t = max(int(w["shape"][0] * args.scale), 1)
+    shape = (n_t,) + tuple(w["shape"][1:])
+    dt = getattr(torch, w["dtype"])
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    base = torch.empty(shape, dtype=dt, device="cuda")
+    for t0 in range(0, n_t, 256):  # in slabs: no second full-size temporary
+        blk = base[t0:t0 + 256]
+        blk.normal_(generator=gen)
+        if w["nan"]:
+            blk[torch.rand(blk.shape, device="cuda", generator=gen) < w["nan"]] = float("nan")
+    arr = base.permute(*range(1, len(shape)), 0)  # (*lead, n_t): zero copy
+    by = (torch.arange(n_t, device="cuda") % w["groups"])
+    kw = dict(expected_groups=np.arange(w["groups"]))
+
+    def singles():
+        return [flox_amd.groupby_reduce(arr, by, func=f, **kw)[0] for f in FUNCS]
+
+    def many_off():
+        with flox_amd.set_options(fused_many=False):
+            return flox_amd.groupby_reduce_many(arr, by, funcs=FUNCS, **kw)[0]
+
+    def many_fused():
+        return flox_amd.groupby_reduce_many(arr, by, funcs=FUNCS, **kw)[0]
+
+    forms = {"singles": singles}
+    if many is not None:
+        forms["many_off"] = many_off
+        forms["many_fused"] = many_fused
+    out = {"workload": name, "shape": list(shape), "root": args.root, "reps": args.reps}
+
+    def timed(fn):
+        ts = []
+        for _ in range(args.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(ts)
+
+    meds = {k: [] for k in forms}
+    for fn in forms.values():
+        for _ in range(2):
+            fn()
+    for _ in range(args.rounds):  # rounds alternate the forms
+        for k, fn in forms.items():
+            meds[k].append(timed(fn))
+    for k in ("singles", "many_off", "many_fused"):
+        m = meds.get(k)
+        out[f"{k}_ms"] = None if m is None else round(statistics.median(m), 4)
+        out[f"{k}_range_ms"] = None if m is None else [round(min(m), 4), round(max(m), 4)]
+
+    # one column pass on its own, device events: the fused set where this
+    # build has it, and the mean's SET_SUM_COUNT for scale
+    m_cols = base[0].numel()
+    vt = base.reshape(n_t, m_cols)
+    sc, perm = torch.sort(by, stable=True)
+    sc, perm = sc.to(torch.int32), perm.to(torch.int32)
+    for label, op in (("summary", _ffi.SET_SUMMARY), ("sum_count", _ffi.SET_SUM_COUNT)):
+        def kern():
+            return aggregate_hip.grouped_partials_cols(op, vt, sc, perm, w["groups"], skipnan=True)
+        try:
+            for _ in range(2):
+                kern()
+        except RuntimeError:  # a build whose column path lacks the set
+            out[f"kernel_{label}_ms"] = None
+            continue
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(args.reps):
+            kern()
+        e1.record()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / args.reps
+        out[f"kernel_{label}_ms"] = round(ms, 4)
+        out[f"kernel_{label}_B_per_element"] = vt.element_size()
+        out[f"kernel_{label}_frac_copy_ceiling"] = round(
+            vt.numel() * vt.element_size() / (ms * 1e-3) / COPY_CEILING, 3)
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -38,6 +137,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--scale", type=float, default=1.0, help="shrink n (rehearsal)")
     ap.add_argument("--only", default=None)
+    ap.add_argument("--cols", action="store_true", help="the column workloads only")
     args = ap.parse_args()
     sys.path.insert(0, args.root)
     import torch
@@ -61,8 +161,12 @@ def main():
             ts.append((time.perf_counter() - t0) * 1e3)
         return statistics.median(ts)
 
+    for name, w in COLS_WORKLOADS.items():
+        if args.only == name or (args.only is None and args.cols):
+            bench_cols(args, torch, flox_amd, name, w)
+
     for name, w in WORKLOADS.items():
-        if args.only and args.only != name:
+        if (args.only and args.only != name) or (args.only is None and args.cols):
             continue
         n = int(w["n"] * args.scale)
         dt = getattr(torch, w["dtype"])
