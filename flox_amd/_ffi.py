@@ -36,6 +36,8 @@ SET_WELFORD = 11
 SET_ARGMIN_PAIR = 12
 SET_ARGMAX_PAIR = 13
 SET_SUMMARY = 14
+SET_ARGMIN_COLS = 15  # column path only (fh_grouped_reduce_cols)
+SET_ARGMAX_COLS = 16
 FLAG_SKIPNAN = 1
 FLAG_FORCE_LDS = 2
 FLAG_FORCE_ATOMIC = 4
@@ -148,8 +150,26 @@ def load_library():
     lib.fh_abi_revision.restype = ctypes.c_int
     if lib.fh_version() != 1 or lib.fh_abi_revision() < 6:
         raise RuntimeError("libfloxhip.so ABI version mismatch")
+    # the column forms of the row-valued sets came without a new revision:
+    # the symbol is how a caller detects them (cols_supports below)
+    if hasattr(lib, "fh_cols_supports"):
+        lib.fh_cols_supports.argtypes = [ctypes.c_int]
+        lib.fh_cols_supports.restype = ctypes.c_int
     _lib = lib
     return lib
+
+
+def cols_supports(op_set: int) -> bool:
+    """Whether fh_grouped_reduce_cols of the loaded library serves op_set. A
+    library without fh_cols_supports predates the row-valued column forms
+    and serves the sets that had one before: all but the index and arg sets."""
+    lib = load_library()
+    if hasattr(lib, "fh_cols_supports"):
+        return lib.fh_cols_supports(op_set) == 1
+    return op_set in (
+        SET_SUM_COUNT, SET_SUM_COUNT_PRESENT, SET_COUNT, SET_MIN_FULL, SET_MIN_COUNT,
+        SET_MAX_FULL, SET_MAX_COUNT, SET_SSD, SET_PROD, SET_WELFORD, SET_SUMMARY,
+    )
 
 
 def check(code: int) -> None:

@@ -73,6 +73,11 @@ _SET_MEMBERS = {
     # or column path; NaN rows touch nothing but nanflag; ssd = f64 M2 about
     # the mean)
     _ffi.SET_SUMMARY: ("sum", "count", "present", "min", "max", "nanflag", "ssd"),
+    # single-pass arg-reductions (cols path only): idx = int64 row of the
+    # extremum, ties to the smallest row, the first NaN row when not skipping
+    # (INT64_MAX where no candidate was seen)
+    _ffi.SET_ARGMIN_COLS: ("idx", "count", "present", "nanflag"),
+    _ffi.SET_ARGMAX_COLS: ("idx", "count", "present", "nanflag"),
 }
 
 IDX_SENTINEL_MIN = (1 << 63) - 1  # untouched IDXMIN bin
@@ -515,6 +520,7 @@ def grouped_partials_cols(
     *,
     means: torch.Tensor | None = None,
     skipnan: bool = False,
+    row_offset: int = 0,
 ) -> dict[str, torch.Tensor]:
     """Grouped reduce over the LEADING axis of a 2-D array (n_t, m) with
     column stride 1 (row stride = values2d.stride(0)). codes_sorted/perm:
@@ -522,7 +528,14 @@ def grouped_partials_cols(
     per-group partials of shape (ngroups, m). SET_SUMMARY: the seven members
     grouped_partials documents, for any group count (the column kernel keeps
     its state in registers); NaN rows only set "nanflag" whatever skipnan
-    says."""
+    says. SET_IDXMIN / SET_IDXMAX: "idx" is the int64 smallest / largest row
+    (+ row_offset) of each (group, column), among its non-NaN rows under
+    skipnan (IDX_SENTINEL_MIN / IDX_SENTINEL_MAX where there is none), with
+    "count" and "present" as in grouped_partials; no target applies here.
+    SET_ARGMIN_COLS / SET_ARGMAX_COLS: "idx" is the row of the extremum from
+    one pass over the values, np.argmin / np.argmax rules for any perm that
+    sorts the codes (ties to the smallest row, -0.0 == +0.0, the first NaN
+    wins unless skipnan), IDX_SENTINEL_MIN where no candidate was seen."""
     lib = _ffi.load_library()
     _require_gpu_tensor(values2d, "values")
     assert values2d.ndim == 2 and values2d.stride(1) == 1
@@ -583,6 +596,10 @@ def grouped_partials_cols(
         dt = torch.float64 if op_set == SET_SSD else _acc_dtype(values2d.dtype)
         out["sum"] = torch.empty(shape, dtype=dt, device=dev)
         c.out_sum = out["sum"].data_ptr()
+    if "idx" in members:
+        out["idx"] = torch.empty(shape, dtype=torch.int64, device=dev)
+        c.out_sum = out["idx"].data_ptr()  # the row rides the out_sum slot
+        c.row_offset = row_offset
     if "count" in members:
         out["count"] = torch.empty(shape, dtype=torch.int64, device=dev)
         c.out_count = out["count"].data_ptr()

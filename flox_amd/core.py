@@ -58,6 +58,11 @@ _ARG_FUNCS = ("argmax", "argmin", "nanargmax", "nanargmin")
 _FIRST_LAST_FUNCS = ("first", "last", "nanfirst", "nanlast")
 _VAR_FUNCS = ("var", "nanvar", "std", "nanstd")
 _LEAD_FOLD_FUNCS = _QUANTILE_FUNCS + ("mode", "nanmode") + _ARG_FUNCS + _FIRST_LAST_FUNCS
+# options.cols_order_funcs: the arg-reductions and first/last over leading
+# dims take the column kernel's row-valued sets where the call is eligible
+# (_cols_order_ok) instead of the lead fold
+COLS_ORDER_FUNCS = True
+_COLS_ORDER = _ARG_FUNCS + _FIRST_LAST_FUNCS
 
 _TORCH_TO_NP = {
     torch.float32: np.dtype("float32"),
@@ -799,7 +804,7 @@ class _Plan:
         "min_count_", "fill_value", "out_dtype",
         # _select_engine, _fold_lead
         "label_src", "row_offset", "cols", "many_served", "lead_folded",
-        "arg_localize_N", "base_ngroups",
+        "arg_localize_N", "base_ngroups", "cols_order",
     )
 
 
@@ -976,12 +981,28 @@ def _fold_lead(p, codes_full, N):
         p.labels = torch.where(natm, torch.full_like(p.labels, -1), p.labels)
 
 
+def _cols_order_ok(p, vt):
+    """Whether an arg-reduction or first/last over leading dims takes the
+    column form. Everything else in _LEAD_FOLD_FUNCS, and these where a
+    condition fails, keeps the lead fold with its results and exceptions."""
+    return (
+        COLS_ORDER_FUNCS
+        and p.func in _COLS_ORDER
+        and vt.dtype in _TORCH_VDTYPE
+        and not p.dist_on
+        and p.inp.dt_dtype is None
+        and p.subset_keep_shape is None
+        and vt.numel() > 0 and p.ngroups > 0
+        and _ffi.cols_supports(_ffi.SET_ARGMAX_COLS)
+    )
+
+
 def _select_engine(p, by):
     """1-D, column (either summary-served inside an eligible
     groupby_reduce_many), or lead-folded. Fills in the plan's engine fields;
     the lead fold (_fold_lead) also rewrites its vals, labels and ngroups."""
     p.label_src, p.row_offset, p.cols = None, p.shard_row_offset, None
-    p.many_served = p.lead_folded = False
+    p.many_served = p.lead_folded = p.cols_order = False
     many, facs = p.many, p.facs
     if p.lead_M == 1:
         # label-code cache key: the CALLER's by object(s) — `labels` is a
@@ -1034,6 +1055,12 @@ def _select_engine(p, by):
                 )
             p.many_served = many.eligible and p.func in FUSED_MANY_FUNCS
         return _EngineColsSummary(p) if p.many_served else _EngineCols(p)
+    if _cols_order_ok(p, vt):
+        # the row-valued column sets: no composite labels, no flattened copy,
+        # one read of the values, no limit on N * lead_M. Inside
+        # groupby_reduce_many these names share the factorization only.
+        p.cols_order = True
+        return _EngineCols(p)
     # (the column view and the sort above go unused here: kept, since
     # dropping them would change which kernels these calls launch)
     _fold_lead(p, codes_full, N)
@@ -1289,6 +1316,30 @@ def _family_first_last(p, eng):
     return gathered, ~valid, pp["count"]
 
 
+def _family_arg_cols(p, eng):
+    """Arg-reductions over leading dims: one SET_ARG*_COLS pass keeps the
+    running extremum and its row per (group, column). The row is already the
+    index within the reduced axes, so nothing is subtracted; the triple is
+    the one _family_arg's two-pass form hands the finalize."""
+    op_set = _ffi.SET_ARGMAX_COLS if "max" in p.func else _ffi.SET_ARGMIN_COLS
+    pp = eng.run(op_set, p.agg.skipnan)
+    result = pp["idx"]
+    empty_mask = (pp["present"] == 0) | (result == _I64_MAX)
+    return result, empty_mask, pp["count"]
+
+
+def _family_first_last_cols(p, eng):
+    """first/last over leading dims: the column form of the func's index set,
+    then a gather from the (N, lead_M) view the kernel read."""
+    vt = p.cols[0]
+    pp = eng.run(p.agg.op_set, p.agg.skipnan)
+    idx = pp["idx"]
+    sentinel = _I64_MAX if p.func in ("first", "nanfirst") else -1
+    valid = idx != sentinel
+    safe = torch.clamp(idx, 0, vt.shape[0] - 1)
+    return torch.gather(vt, 0, safe), ~valid, pp["count"]
+
+
 def _var_from_ssd(p, ssd, counts):
     den = counts.to(torch.float64) - p.ddof
     result = ssd / den
@@ -1370,6 +1421,8 @@ def _select_family(p):
         return _family_quantile
     if func in ("mode", "nanmode"):
         return _family_mode
+    if p.cols_order:
+        return _family_arg_cols if func in _ARG_FUNCS else _family_first_last_cols
     if func in _ARG_FUNCS:
         return _family_arg
     if func in _FIRST_LAST_FUNCS:

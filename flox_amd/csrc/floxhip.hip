@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <type_traits>
+#include <limits>
 #include <cstdio>
 #include <cstdlib>
 
@@ -77,7 +78,14 @@ enum {
   B_MOM2 = 4096,   /* pivoted single-pass second moment (FH_SET_SUMMARY); with
                       it B_MIN and B_MAX may both be set: min keeps
                       minmax_off, max takes max_off */
+  /* single-pass arg-reductions of the column path (FH_SET_ARG*_COLS): the
+   * running extremum, its row and the first NaN row per (group, column) */
+  B_ARGMINC = 8192,
+  B_ARGMAXC = 16384,
 };
+constexpr int B_ARGC = B_ARGMINC | B_ARGMAXC;
+/* the sets k_order_cols serves */
+constexpr int B_ORDERC = B_IDXMIN | B_IDXMAX | B_ARGC;
 constexpr int OPS_SUMMARY = B_SUM | B_CNT | B_MIN | B_MAX | B_NANFLAG | B_MOM2;
 
 __host__ __device__ constexpr int set_bits(int op_set) {
@@ -97,6 +105,8 @@ __host__ __device__ constexpr int set_bits(int op_set) {
     case FH_SET_ARGMIN_PAIR: return B_MIN | B_CNT | B_PRESENT | B_NANFLAG | B_ARGROW;
     case FH_SET_ARGMAX_PAIR: return B_MAX | B_CNT | B_PRESENT | B_NANFLAG | B_ARGROW;
     case FH_SET_SUMMARY: return B_SUM | B_CNT | B_MIN | B_MAX | B_NANFLAG | B_MOM2;
+    case FH_SET_ARGMIN_COLS: return B_ARGMINC | B_CNT | B_PRESENT | B_NANFLAG;
+    case FH_SET_ARGMAX_COLS: return B_ARGMAXC | B_CNT | B_PRESENT | B_NANFLAG;
     default: return 0;
   }
 }
@@ -231,6 +241,10 @@ struct BinLayout {
    * the min), the pivot x0, s1 and s2 (in the slab: the block's mean as
    * x0 + s1/n, and its M2) */
   int64_t max_off, s1_off, s2_off, pivot_off;
+  /* B_ARGC only (the column path's slab), carved last: the chunk's extremum
+   * as the value's own bits, and its first NaN row (int64); the extremum's
+   * row has sum_off */
+  int64_t argval_off, nanrow_off;
 };
 
 template <typename V>
@@ -242,7 +256,7 @@ __host__ __device__ BinLayout bin_layout(int bits, int64_t ngroups, int64_t cnt_
     off += ((ngroups * elem + 255) / 256) * 256; /* 256-B aligned sections */
     return o;
   };
-  L.sum_off = (bits & (B_SUM | B_SSD | B_PROD | B_IDXMIN | B_IDXMAX | B_WELFORD)) ? carve(8) : -1;
+  L.sum_off = (bits & (B_SUM | B_SSD | B_PROD | B_IDXMIN | B_IDXMAX | B_WELFORD | B_ARGC)) ? carve(8) : -1;
   L.cnt_off = (bits & B_CNT) ? carve(cnt_elem_size) : -1;
   L.present_off = (bits & B_PRESENT) ? carve(4) : -1;
   L.minmax_off = (bits & (B_MIN | B_MAX)) ? carve(sizeof(typename Traits<V>::Enc)) : -1;
@@ -254,6 +268,11 @@ __host__ __device__ BinLayout bin_layout(int bits, int64_t ngroups, int64_t cnt_
     L.s1_off = carve(8);
     L.s2_off = carve(8);
     L.pivot_off = carve(sizeof(typename Traits<V>::Enc));
+  }
+  L.argval_off = L.nanrow_off = -1;
+  if (bits & B_ARGC) {
+    L.argval_off = carve(sizeof(V));
+    L.nanrow_off = carve(8);
   }
   L.bytes = off;
   return L;
@@ -663,6 +682,36 @@ __global__ void k_combine(const char* __restrict__ slab, int nblocks,
     ((V*)out_min)[g] = c != 0 ? TR::dec(mn) : TR::pos_inf();
     ((V*)out_max)[g] = c != 0 ? TR::dec(mx) : (V)-TR::pos_inf();
     out_ssd[g] = m2 > 0.0 ? m2 : 0.0;
+    return;
+  }
+  if constexpr ((OPS & B_ARGC) != 0) {
+    /* (value, row, NaN row) per chunk: the better value wins, equal values
+     * (==, so -0.0 ties +0.0) the smaller row; the smallest NaN row beats
+     * every value. A skipping chunk never writes a NaN row. */
+    constexpr bool ISMAX = (OPS & B_ARGMAXC) != 0;
+    int64_t c = 0, row = INT64_MAX, nanrow = INT64_MAX;
+    uint32_t p = 0, nf = 0;
+    V best = (V)0;
+    for (int b = 0; b < nblocks; ++b) {
+      const char* blk = slab + (int64_t)b * lay.bytes;
+      c += (int64_t)((const uint32_t*)(blk + lay.cnt_off))[g];
+      p |= ((const uint32_t*)(blk + lay.present_off))[g];
+      nf |= ((const uint32_t*)(blk + lay.nanflag_off))[g];
+      const int64_t nr = ((const int64_t*)(blk + lay.nanrow_off))[g];
+      nanrow = nr < nanrow ? nr : nanrow;
+      const int64_t r = ((const int64_t*)(blk + lay.sum_off))[g];
+      if (r == INT64_MAX) continue;
+      const V x = ((const V*)(blk + lay.argval_off))[g];
+      const bool better = ISMAX ? x > best : x < best;
+      if (row == INT64_MAX || better || (x == best && r < row)) {
+        best = x;
+        row = r;
+      }
+    }
+    ((int64_t*)out_sum)[g] = nanrow != INT64_MAX ? nanrow : row;
+    out_count[g] = c;
+    out_present[g] = p;
+    out_nanflag[g] = nf;
     return;
   }
   SumT s = IS_PROD ? (SumT)1 : (SumT)0;
@@ -1259,6 +1308,189 @@ __launch_bounds__(COLS_BLOCK) __global__ void k_reduce_cols(
 #pragma unroll
         for (int k = 0; k < VC; ++k)
           consume((c0 + k < m) ? values[row + c0 + k] : (V)0, k, c0 + k < m);
+        ++i;
+      }
+    }
+  }
+  flush(cur_g);
+}
+
+/* identities of a running max / min over V: no value is below / above them */
+template <typename V>
+__host__ __device__ constexpr V cols_lowest() {
+  return std::numeric_limits<V>::has_infinity ? -std::numeric_limits<V>::infinity()
+                                              : std::numeric_limits<V>::lowest();
+}
+template <typename V>
+__host__ __device__ constexpr V cols_highest() {
+  return std::numeric_limits<V>::has_infinity ? std::numeric_limits<V>::infinity()
+                                              : std::numeric_limits<V>::max();
+}
+
+/* ---- column path, order-dependent sets ------------------------------------
+ * k_reduce_cols' walk (rows in group order, staged code/perm tiles, VC columns
+ * per thread, the three flush modes) for the sets whose state is a ROW:
+ *   B_IDXMIN / B_IDXMAX  the smallest / largest original row perm[i] of the
+ *                        segment (non-NaN rows only when SKIP): first / last;
+ *   B_ARGMINC / B_ARGMAXC  the running extremum bv, its row brow and the
+ *                        first NaN row nrow, one pass: arg-reductions.
+ * Rows are kept as int32 (n_t < 2^31) and widened, + row_offset, at the
+ * flush; NONE (INT32_MAX, or -1 for IDXMAX) becomes the 1-D sentinel. The
+ * extremum starts at its identity with row NONE, so "better, or equal and an
+ * earlier row" also admits the first candidate; the row compare makes ties go
+ * to the smallest row under any perm that sorts the codes, and == makes
+ * -0.0 tie +0.0. Address arithmetic is row * ldm + c0 in 64 bits. */
+template <typename V, int OPS, int VC, bool SLAB, bool SKIP>
+__launch_bounds__(COLS_BLOCK) __global__ void k_order_cols(
+    const V* __restrict__ values, const int* __restrict__ codes_sorted,
+    const int* __restrict__ perm, int64_t n_t, int64_t m, int64_t ldm,
+    int64_t row_offset, int64_t chunk_rows,
+    const int64_t* __restrict__ chunk_offs, char* __restrict__ slab,
+    BinLayout lay, int64_t* out_idx, int64_t* out_count, uint32_t* out_present,
+    uint32_t* out_nanflag) {
+  using TR = Traits<V>;
+  constexpr bool ARG = (OPS & B_ARGC) != 0;
+  constexpr bool ISMAX = (OPS & (B_ARGMAXC | B_IDXMAX)) != 0;
+  static_assert((OPS & B_ORDERC) != 0 && (OPS & B_CNT) && (OPS & B_PRESENT),
+                "row-valued sets only");
+  /* "no row": IDXMAX folds with max, everything else with min */
+  constexpr int NONE = (OPS & B_IDXMAX) ? -1 : INT32_MAX;
+  constexpr V START = ISMAX ? cols_lowest<V>() : cols_highest<V>();
+
+  __shared__ int s_code[COLS_TTILE];
+  __shared__ int s_perm[COLS_TTILE];
+
+  const int64_t c0 = ((int64_t)blockIdx.x * COLS_BLOCK + threadIdx.x) * VC;
+  const bool full = c0 + VC <= m;
+  int64_t t_begin, t_end;
+  if (chunk_offs) {
+    t_begin = chunk_offs[blockIdx.y];
+    t_end = chunk_offs[blockIdx.y + 1];
+  } else {
+    t_begin = (int64_t)blockIdx.y * chunk_rows;
+    t_end = (t_begin + chunk_rows < n_t) ? t_begin + chunk_rows : n_t;
+  }
+  char* my_slab = SLAB ? slab + (int64_t)blockIdx.y * lay.bytes : nullptr;
+
+  int brow[VC];
+  uint32_t cnt[VC];
+  V bv[ARG ? VC : 1];
+  int nrow[ARG ? VC : 1];
+  int cur_g = -1;
+
+  auto reset = [&]() {
+#pragma unroll
+    for (int k = 0; k < VC; ++k) {
+      brow[k] = NONE;
+      cnt[k] = 0;
+      if constexpr (ARG) {
+        bv[k] = START;
+        nrow[k] = INT32_MAX;
+      }
+    }
+  };
+  reset();
+
+  auto widen = [&](int r) -> int64_t {
+    if (r == NONE) return (OPS & B_IDXMAX) ? (int64_t)-1 : INT64_MAX;
+    return (int64_t)r + row_offset;
+  };
+
+  auto flush = [&](int g) {
+    if (g < 0) return;
+#pragma unroll
+    for (int k = 0; k < VC; ++k) {
+      if (c0 + k >= m) break;
+      const int64_t o = (int64_t)g * m + c0 + k;
+      if (SLAB) {
+        ((int64_t*)(my_slab + lay.sum_off))[o] = widen(brow[k]);
+        ((uint32_t*)(my_slab + lay.cnt_off))[o] = cnt[k];
+        ((uint32_t*)(my_slab + lay.present_off))[o] = 1u;
+        if constexpr (ARG) {
+          ((V*)(my_slab + lay.argval_off))[o] = bv[k];
+          ((int64_t*)(my_slab + lay.nanrow_off))[o] =
+              (SKIP || nrow[k] == INT32_MAX) ? INT64_MAX : (int64_t)nrow[k] + row_offset;
+          ((uint32_t*)(my_slab + lay.nanflag_off))[o] = nrow[k] != INT32_MAX ? 1u : 0u;
+        }
+      } else {
+        int r = brow[k];
+        if constexpr (ARG) {
+          if (!SKIP && nrow[k] != INT32_MAX) r = nrow[k]; /* the first NaN wins */
+          out_nanflag[o] = nrow[k] != INT32_MAX ? 1u : 0u;
+        }
+        out_idx[o] = widen(r);
+        out_count[o] = (int64_t)cnt[k];
+        out_present[o] = 1u;
+      }
+    }
+  };
+
+  auto consume = [&](V v, int k, int row) {
+    const bool vnan = TR::isnan_(v);
+    if constexpr (ARG) {
+      if (vnan) {
+        nrow[k] = row < nrow[k] ? row : nrow[k];
+        return;
+      }
+      cnt[k] += 1u;
+      const bool better = ISMAX ? v > bv[k] : v < bv[k];
+      const bool take = better || (v == bv[k] && row < brow[k]);
+      bv[k] = take ? v : bv[k];
+      brow[k] = take ? row : brow[k];
+    } else {
+      if constexpr (SKIP) {
+        if (vnan) return;
+      }
+      cnt[k] += vnan ? 0u : 1u;
+      if (OPS & B_IDXMIN) brow[k] = row < brow[k] ? row : brow[k];
+      if (OPS & B_IDXMAX) brow[k] = row > brow[k] ? row : brow[k];
+    }
+  };
+
+  for (int64_t t0 = t_begin; t0 < t_end; t0 += COLS_TTILE) {
+    const int nt = (int)((t_end - t0 < COLS_TTILE) ? (t_end - t0) : COLS_TTILE);
+    __syncthreads();
+    for (int i = threadIdx.x; i < nt; i += COLS_BLOCK) {
+      s_code[i] = codes_sorted[t0 + i];
+      s_perm[i] = perm[t0 + i];
+    }
+    __syncthreads();
+    const bool col_act = c0 < m;
+    int i = 0;
+    while (i < nt) {
+      const int g = s_code[i];
+      if (g != cur_g) {
+        flush(cur_g);
+        reset();
+        cur_g = g;
+      }
+      if (g < 0 || !col_act) {
+        ++i;
+        continue;
+      }
+      const int pa = s_perm[i];
+      if (VC > 1 && full) {
+        /* two rows of the same segment per iteration, as k_reduce_cols */
+        if (i + 1 < nt && s_code[i + 1] == g) {
+          const int pb = s_perm[i + 1];
+          Vec<V, VC> va = *reinterpret_cast<const Vec<V, VC>*>(values + (int64_t)pa * ldm + c0);
+          Vec<V, VC> vb = *reinterpret_cast<const Vec<V, VC>*>(values + (int64_t)pb * ldm + c0);
+#pragma unroll
+          for (int k = 0; k < VC; ++k) consume(va.v[k], k, pa);
+#pragma unroll
+          for (int k = 0; k < VC; ++k) consume(vb.v[k], k, pb);
+          i += 2;
+          continue;
+        }
+        Vec<V, VC> vv = *reinterpret_cast<const Vec<V, VC>*>(values + (int64_t)pa * ldm + c0);
+#pragma unroll
+        for (int k = 0; k < VC; ++k) consume(vv.v[k], k, pa);
+        ++i;
+      } else {
+        const int64_t row = (int64_t)pa * ldm;
+#pragma unroll
+        for (int k = 0; k < VC; ++k)
+          if (c0 + k < m) consume(values[row + c0 + k], k, pa);
         ++i;
       }
     }
@@ -2014,6 +2246,8 @@ struct BinPtrs {
   /* B_MOM2: the M2 bins (out_ssd, or a chunk's s2 section). `present` is
    * then null in a slab, which has no such section for the set. */
   void* ssd;
+  /* B_ARGC: a chunk's first-NaN-row section; null for the output arrays */
+  void* nanrow;
 };
 
 inline BinPtrs out_bins(const fh_call* c) {
@@ -2029,7 +2263,8 @@ inline BinPtrs slab_bins(char* s, const BinLayout& lay) {
   return {s + lay.sum_off, s + lay.cnt_off,
           mom2 ? nullptr : s + lay.present_off, s + lay.minmax_off,
           s + (mom2 ? lay.max_off : lay.minmax_off), s + lay.nanflag_off,
-          s + lay.sumx_off, 4, mom2 ? s + lay.s2_off : nullptr};
+          s + lay.sumx_off, 4, mom2 ? s + lay.s2_off : nullptr,
+          lay.nanrow_off >= 0 ? s + lay.nanrow_off : nullptr};
 }
 
 /* identity-fill every section of OPS: min bins 0xFF.., max bins 0x00.. (the
@@ -2041,7 +2276,10 @@ int init_bins(const BinPtrs& b, int64_t nbins, hipStream_t stream) {
   using TR = Traits<V>;
   if (OPS & (B_SUM | B_SSD | B_WELFORD)) FH_CHECK(hipMemsetAsync(b.sum, 0, nbins * 8, stream));
   if (OPS & B_WELFORD) FH_CHECK(hipMemsetAsync(b.sumx, 0, nbins * 8, stream));
-  if (OPS & (B_IDXMIN | B_ARGROW)) FH_CHECK(fill_bins(b.sum, nbins, (int64_t)INT64_MAX, stream));
+  if (OPS & (B_IDXMIN | B_ARGROW | B_ARGC)) FH_CHECK(fill_bins(b.sum, nbins, (int64_t)INT64_MAX, stream));
+  /* a chunk's extremum section stays unwritten: the merge skips a side
+   * whose row is the sentinel */
+  if ((OPS & B_ARGC) && b.nanrow) FH_CHECK(fill_bins(b.nanrow, nbins, (int64_t)INT64_MAX, stream));
   if (OPS & B_IDXMAX) FH_CHECK(fill_bins(b.sum, nbins, (int64_t)-1, stream));
   if (OPS & B_PROD) FH_CHECK(fill_bins(b.sum, nbins, (typename TR::Acc)1, stream));
   if (OPS & B_CNT) FH_CHECK(hipMemsetAsync(b.cnt, 0, nbins * b.cnt_bytes, stream));
@@ -2604,6 +2842,8 @@ int with_ops(int op_set, F&& f) {
     FH_OPS_CASE(FH_SET_ARGMIN_PAIR)
     FH_OPS_CASE(FH_SET_ARGMAX_PAIR)
     FH_OPS_CASE(FH_SET_SUMMARY)
+    FH_OPS_CASE(FH_SET_ARGMIN_COLS)
+    FH_OPS_CASE(FH_SET_ARGMAX_COLS)
 #undef FH_OPS_CASE
     default: return 4;
   }
@@ -2620,6 +2860,8 @@ int dispatch_ops(fh_call* c) {
     constexpr int OPS = decltype(ops)::value;
     if constexpr ((OPS & B_WELFORD) != 0) {
       return 4; /* column path only */
+    } else if constexpr ((OPS & B_ARGC) != 0) {
+      return 18; /* column path only */
     } else if constexpr ((OPS & B_ARGROW) != 0) {
       if constexpr (CodeWidth<L>::value != 0)
         return 12; /* partition path only: no compact-code form */
@@ -2661,6 +2903,20 @@ int dispatch_label(fh_call* c) {
 #endif
 template <typename V>
 constexpr int COLS_SUMMARY_VC = sizeof(V) == 4 ? FH_COLS_SUMMARY_VC4B : FH_COLS_SUMMARY_VC8B;
+/* columns per thread of the row-valued sets (k_order_cols), by value size:
+ * the arg sets keep 4 (4-byte) or 5 (8-byte) VGPRs per column, the index
+ * sets 2. 4-byte dtypes take one 16-B vector, not k_reduce_cols' two: 8
+ * columns measured 12 % slower for the arg sets (85 against 65 VGPRs) and
+ * 5 % slower for the index sets (profiles/r08_cols_order.md has the resource
+ * report and the measurement) */
+#ifndef FH_COLS_ORDER_VC4B
+#define FH_COLS_ORDER_VC4B 4
+#endif
+#ifndef FH_COLS_ORDER_VC8B
+#define FH_COLS_ORDER_VC8B 2
+#endif
+template <typename V>
+constexpr int COLS_ORDER_VC = sizeof(V) == 4 ? FH_COLS_ORDER_VC4B : FH_COLS_ORDER_VC8B;
 
 struct ColsPlan {
   int vc;
@@ -2684,6 +2940,7 @@ ColsPlan cols_plan(const fh_call* c) {
     /* narrower loads are aligned wherever wider ones are */
     p.vc = p.vc >= COLS_SUMMARY_VC<V> ? COLS_SUMMARY_VC<V> : 1;
   }
+  if ((set_bits(c->op_set) & B_ORDERC) && p.vc > COLS_ORDER_VC<V>) p.vc = COLS_ORDER_VC<V>;
   p.ncolblk = (c->m + (int64_t)COLS_BLOCK * p.vc - 1) / ((int64_t)COLS_BLOCK * p.vc);
   if (p.ncolblk == 0) p.ncolblk = 1;
   int want = (int)((2048 + p.ncolblk - 1) / p.ncolblk);
@@ -2774,12 +3031,83 @@ int launch_cols(fh_call* c) {
   return 0;
 }
 
+/* the row-valued sets: same plan, init, chunking and combine as launch_cols,
+ * k_order_cols in place of k_reduce_cols */
+template <typename V, int OPS>
+int launch_order_cols(fh_call* c) {
+  hipStream_t stream = (hipStream_t)c->stream;
+  const int64_t nbins = c->ngroups * c->m;
+  ColsPlan plan = cols_plan<V>(c);
+  const bool aligned_chunks = c->chunk_offsets != nullptr && c->nchunks > 0;
+  if (aligned_chunks) plan.nchunks = (int)c->nchunks;
+  const bool slab_mode = !aligned_chunks && plan.nchunks > 1;
+  const bool skipnan = (c->flags & FH_SKIPNAN) != 0;
+
+  if (slab_mode) {
+    if ((int64_t)plan.nchunks * plan.lay.bytes > c->scratch_bytes) return 3;
+    for (int ch = 0; ch < plan.nchunks; ++ch) {
+      char* s = (char*)c->scratch + (int64_t)ch * plan.lay.bytes;
+      FH_TRY((init_bins<V, OPS>(slab_bins(s, plan.lay), nbins, stream)));
+    }
+  } else {
+    FH_TRY((init_bins<V, OPS>(out_bins(c), nbins, stream)));
+  }
+
+  dim3 grid((uint32_t)plan.ncolblk, (uint32_t)plan.nchunks);
+  const int64_t* offs = aligned_chunks ? (const int64_t*)c->chunk_offsets : nullptr;
+  auto launch = [&](auto vc, auto slab, auto skip) -> int {
+    auto kern = k_order_cols<V, OPS, decltype(vc)::value, decltype(slab)::value,
+                             decltype(skip)::value>;
+    hipLaunchKernelGGL(kern, grid, dim3(COLS_BLOCK), 0, stream,
+                       (const V*)c->values, (const int*)c->labels,
+                       (const int*)c->perm, c->n, c->m, c->ldm, c->row_offset,
+                       plan.chunk_rows, offs, (char*)c->scratch, plan.lay,
+                       (int64_t*)c->out_sum, c->out_count, c->out_present,
+                       c->out_nanflag);
+    FH_CHECK(hipGetLastError());
+    return 0;
+  };
+  /* columns per thread: COLS_ORDER_VC, the dtype's 16-B vector below it, 1 */
+  auto with_vc = [&](auto f) -> int {
+    if (plan.vc == COLS_ORDER_VC<V>) return f(std::integral_constant<int, COLS_ORDER_VC<V>>{});
+    if constexpr (COLS_ORDER_VC<V> != Traits<V>::VEC) {
+      if (plan.vc == Traits<V>::VEC) return f(std::integral_constant<int, Traits<V>::VEC>{});
+    }
+    return f(std::integral_constant<int, 1>{});
+  };
+  FH_TRY(with_vc([&](auto vc) {
+    return with_bool(slab_mode, [&](auto slab) {
+      return with_bool(skipnan, [&](auto skip) { return launch(vc, slab, skip); });
+    });
+  }));
+
+  if (slab_mode) {
+    hipLaunchKernelGGL((k_combine<V, OPS>), dim3(grid_for(nbins), 1), dim3(256),
+                       0, stream, (const char*)c->scratch, plan.nchunks, nbins,
+                       plan.lay, c->out_sum, c->out_count, c->out_present,
+                       c->out_min, c->out_max, c->out_nanflag,
+                       (double*)c->out_ssd);
+    FH_CHECK(hipGetLastError());
+  }
+  c->path_used = 3;
+  return 0;
+}
+
+/* whether fh_grouped_reduce_cols has a form of the set */
+constexpr bool cols_serves(int bits) { return bits != 0 && !(bits & B_ARGROW); }
+
 template <typename V>
 int dispatch_cols_ops(fh_call* c) {
   return with_ops(c->op_set, [&](auto ops) -> int {
     constexpr int OPS = decltype(ops)::value;
-    if constexpr ((OPS & (B_IDXMIN | B_IDXMAX | B_ARGROW)) != 0) {
+    if constexpr (!cols_serves(OPS)) {
       return 4; /* no column form */
+    } else if constexpr ((OPS & B_ORDERC) != 0) {
+      if (c->target) return 19;
+      if (!c->out_sum || !c->out_count || !c->out_present ||
+          ((OPS & B_NANFLAG) && !c->out_nanflag))
+        return 6;
+      return launch_order_cols<V, OPS>(c);
     } else if constexpr ((OPS & B_MOM2) != 0) {
       if (!c->out_ssd) return 16;
       if (!c->out_sum || !c->out_count || !c->out_present || !c->out_min ||
@@ -2918,10 +3246,13 @@ int fh_grouped_reduce(fh_call* c) {
   if (!c || !c->values || !c->labels) return 6;
   if (c->labels2 && c->g0 * c->g1 != c->ngroups) return 7;
   if (c->op_set == FH_SET_SSD && !c->means) return 8;
+  if (set_bits(c->op_set) & B_ARGC) return 18;
   return with_vdtype(c->vdtype, 9, [&](auto t) {
     return dispatch_label<typename decltype(t)::type>(c);
   });
 }
+
+int fh_cols_supports(int op_set) { return cols_serves(set_bits(op_set)) ? 1 : 0; }
 
 
 int fh_grouped_reduce_cols(fh_call* c) {
@@ -2985,7 +3316,7 @@ const char* fh_error_string(int code) {
     case 3: return "scratch buffer too small (call fh_scratch_bytes)";
     case 4: return "unknown op_set";
     case 5: return "unknown label dtype";
-    case 6: return "null values/labels pointer, or a missing output buffer of FH_SET_SUMMARY";
+    case 6: return "null values/labels pointer, or a missing output buffer of FH_SET_SUMMARY or of a row-valued set on the column path";
     case 7: return "labels2 given but g0*g1 != ngroups";
     case 8: return "FH_SET_SSD requires means";
     case 9: return "unknown value dtype";
@@ -2996,6 +3327,8 @@ const char* fh_error_string(int code) {
     case 15: return "fh_grouped_reduce serves FH_SET_SUMMARY on the LDS-binned path only (bins within LDS, no FH_FORCE_ATOMIC; see fh_query_path)";
     case 16: return "FH_SET_SUMMARY requires out_ssd";
     case 17: return "packed code width must be 12 or 14";
+    case 18: return "FH_SET_ARGMIN_COLS/FH_SET_ARGMAX_COLS exist on the column path only (fh_grouped_reduce_cols; see fh_cols_supports)";
+    case 19: return "fh_grouped_reduce_cols takes no target: FH_SET_IDXMIN/IDXMAX there keep every (non-NaN under FH_SKIPNAN) row as a candidate";
     default: return code >= 1000 ? hipGetErrorString((hipError_t)(code - 1000)) : "unknown error";
   }
 }

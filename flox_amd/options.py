@@ -24,6 +24,14 @@ Supported options:
       count family shares one SET_SUMMARY pass on eligible calls: on the
       LDS-binned path without leading dims, on the column path (any group
       count) with them (core.py).
+  cols_order_funcs: False sends argmax/argmin/nanargmax/nanargmin and
+      first/last/nanfirst/nanlast over leading dims through the lead fold
+      (composite int64 labels over the flattened array, limited to
+      N * lead_M < 2**31); on (the default) they take the column kernel's
+      row-valued sets, which read the caller's strided view in place, once,
+      at any size, where the call is eligible: f32/f64/i32/i64 values after
+      normalisation, not distributed, no datetime values, no axis subset,
+      at least one row and one group (core.py).
 """
 
 from __future__ import annotations
@@ -40,6 +48,7 @@ OPTIONS = {
     "label_code_pack_min_rows": None,  # None = the measured default
     "fused_finalize": None,           # None = on
     "fused_many": None,               # None = on
+    "cols_order_funcs": None,         # None = on
 }
 
 _CACHE_FIELDS = {
@@ -78,6 +87,11 @@ def _apply(name, value):
         if value is not None:
             core.FUSED_MANY = bool(value)
         return ("fused_many", old)
+    if name == "cols_order_funcs":
+        old = core.COLS_ORDER_FUNCS
+        if value is not None:
+            core.COLS_ORDER_FUNCS = bool(value)
+        return ("cols_order_funcs", old)
     if name == "sparse_combine_ngroups":
         old = distributed.SPARSE_NGROUPS
         if value is not None:
@@ -106,6 +120,8 @@ def _restore(name, old):
         core.FUSED_FINALIZE = old
     elif name == "fused_many":
         core.FUSED_MANY = old
+    elif name == "cols_order_funcs":
+        core.COLS_ORDER_FUNCS = old
     elif name == "sparse_combine_ngroups":
         distributed.SPARSE_NGROUPS = old
     elif name == "sparse_combine_fraction":

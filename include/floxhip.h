@@ -72,7 +72,13 @@ enum fh_opset {
    * FH_SKIPNAN) row is. IDXMIN keeps the smallest row index, IDXMAX the
    * largest; out_count/out_present as usual; the index (+ row_offset, for
    * multi-GPU shards) lands in out_sum as int64, -2^63.. sentinel for
-   * untouched groups handled by init (IDXMIN: INT64_MAX, IDXMAX: -1). */
+   * untouched groups handled by init (IDXMIN: INT64_MAX, IDXMAX: -1).
+   * fh_grouped_reduce_cols serves both sets without `target` (error 19 with
+   * one): per (group, column) the smallest / largest original row perm[i]
+   * (+ row_offset) among the group's rows, the non-NaN ones under
+   * FH_SKIPNAN; out_sum is int64 (ngroups, m) with the same sentinels, and
+   * out_count / out_present mean what they mean in 1-D: non-NaN rows, any
+   * row seen. */
   FH_SET_IDXMIN = 9,
   FH_SET_IDXMAX = 10,
   /* single-pass variance partials for the COLUMN path only: per (group,
@@ -122,6 +128,23 @@ enum fh_opset {
    * out_ssd, 6 without another member's buffer. No finish mode applies
    * (error 14). */
   FH_SET_SUMMARY = 14,
+  /* single-pass arg-reductions, COLUMN path only (fh_grouped_reduce returns
+   * error 18 without launching): each thread keeps, per column, the running
+   * extremum of the segment, its row, the first NaN row and the non-NaN
+   * count in registers, so the values are read once. Outputs, (ngroups, m):
+   * out_sum = int64 original row perm[i] + row_offset of the extremum
+   * (INT64_MAX where no candidate was seen), out_count = non-NaN rows,
+   * out_present = any row seen, out_nanflag = a NaN row seen. Ties go to the
+   * smallest row (np.argmin / np.argmax) under ANY perm that sorts the
+   * codes: equal values compare rows. Equality is that of the values
+   * (-0.0 == +0.0), not of an encoding. Without FH_SKIPNAN the smallest NaN
+   * row of a group wins and stays the winner; with it NaN rows are no
+   * candidates, do not count, and still set out_nanflag. Where the row range
+   * is split without group alignment, each chunk writes (value, row, NaN
+   * row) and the combine merges them by the same rules. `target` is refused
+   * (error 19). */
+  FH_SET_ARGMIN_COLS = 15,
+  FH_SET_ARGMAX_COLS = 16,
 };
 
 /* flags */
@@ -244,6 +267,11 @@ int fh_grouped_reduce(fh_call* c);
  * computed without offsetting labels: one segmented pass per column) */
 int fh_grouped_reduce_cols(fh_call* c);
 
+/* 1 where fh_grouped_reduce_cols serves the op set, 0 where it does not (an
+ * unknown set included). Libraries older than the column forms of
+ * FH_SET_IDXMIN/IDXMAX and FH_SET_ARG*_COLS lack the symbol. */
+int fh_cols_supports(int op_set);
+
 /* pack (order-preserving 32-bit value encoding, global row index) into one
  * int64 key per row, so that a grouped MIN over the keys is argmin/argmax
  * with np.argmin's first-occurrence tie-break (the packed form of the
@@ -270,7 +298,10 @@ int fh_version(void);
  * FH_SET_SUMMARY and out_ssd; 5 added FH_L_P12/FH_L_P14, fh_pack_codes and
  * fh_packed_code_bytes; 6 added FH_SET_SUMMARY to fh_grouped_reduce_cols. A
  * caller built against revision R
- * needs a library with fh_abi_revision() >= R. */
+ * needs a library with fh_abi_revision() >= R. The column forms of
+ * FH_SET_IDXMIN/IDXMAX, FH_SET_ARGMIN_COLS/ARGMAX_COLS and fh_cols_supports
+ * came without a new revision (it stays 6: fh_call is unchanged): a caller
+ * detects them by the fh_cols_supports symbol and its answer. */
 int fh_abi_revision(void);
 
 #ifdef __cplusplus
