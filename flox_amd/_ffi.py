@@ -155,8 +155,25 @@ def load_library():
     if hasattr(lib, "fh_cols_supports"):
         lib.fh_cols_supports.argtypes = [ctypes.c_int]
         lib.fh_cols_supports.restype = ctypes.c_int
+    # likewise the sort-in-LDS column form of the quantile family
+    if hasattr(lib, "fh_grouped_quantile_cols"):
+        lib.fh_grouped_quantile_cols.argtypes = [
+            ctypes.POINTER(FhCall), ctypes.c_int, ctypes.c_int64,
+        ]
+        lib.fh_grouped_quantile_cols.restype = ctypes.c_int
+        lib.fh_quantile_cols_max_rows.argtypes = [ctypes.c_int]
+        lib.fh_quantile_cols_max_rows.restype = ctypes.c_int64
     _lib = lib
     return lib
+
+
+def quantile_cols_max_rows(vdtype: int) -> int:
+    """The longest group fh_grouped_quantile_cols can stage for this value
+    dtype; 0 where the loaded library predates the entry."""
+    lib = load_library()
+    if not hasattr(lib, "fh_grouped_quantile_cols"):
+        return 0
+    return int(lib.fh_quantile_cols_max_rows(vdtype))
 
 
 def cols_supports(op_set: int) -> bool:
@@ -172,7 +189,15 @@ def cols_supports(op_set: int) -> bool:
     )
 
 
+# codes of fh_grouped_quantile_cols, which fh_error_string predates
+_QCOLS_ERRORS = {
+    20: "max_seg_rows exceeds fh_quantile_cols_max_rows for the value dtype",
+    21: "fh_grouped_quantile_cols: missing values/labels/perm/out_sum buffer, "
+        "missing q array, or an extent that is negative or beyond int32 rows",
+}
+
+
 def check(code: int) -> None:
     if code != 0:
-        msg = load_library().fh_error_string(code).decode()
+        msg = _QCOLS_ERRORS.get(code) or load_library().fh_error_string(code).decode()
         raise RuntimeError(f"floxhip error {code}: {msg}")

@@ -737,6 +737,92 @@ def grouped_mode(
     return out
 
 
+def _sorted_cols(values2d, codes_sorted, perm, ngroups, q_t, *, skipnan, max_seg_rows, want_count):
+    # one fh_grouped_quantile_cols call: q_t None = mode
+    lib = _ffi.load_library()
+    if not hasattr(lib, "fh_grouped_quantile_cols"):
+        raise RuntimeError("libfloxhip.so lacks fh_grouped_quantile_cols: rebuild the extension")
+    _require_gpu_tensor(values2d, "values")
+    assert values2d.ndim == 2 and values2d.stride(1) == 1
+    assert codes_sorted.dtype == torch.int32 and perm.dtype == torch.int32
+    if values2d.dtype not in _TORCH_VDTYPE:
+        raise NotImplementedError(f"engine=hip does not support values dtype {values2d.dtype}")
+    n_t, m = values2d.shape
+    dev = values2d.device
+    nq = 0 if q_t is None else q_t.numel()
+    c = FhCall()
+    c.vdtype = _TORCH_VDTYPE[values2d.dtype]
+    c.ldtype = _ffi.L_I32
+    c.flags = FLAG_SKIPNAN if skipnan else 0
+    c.n = n_t
+    c.m = m
+    c.ldm = values2d.stride(0)
+    c.ngroups = ngroups
+    c.values = values2d.data_ptr()
+    codes_sorted = codes_sorted.contiguous()
+    perm = perm.contiguous()
+    c.labels = codes_sorted.data_ptr()
+    c.perm = perm.data_ptr()
+    if q_t is None:
+        out = torch.empty((ngroups, m), dtype=values2d.dtype, device=dev)
+    else:
+        out = torch.empty((nq, ngroups, m), dtype=torch.float64, device=dev)
+        c.means = q_t.data_ptr()
+    c.out_sum = out.data_ptr()
+    count = None
+    if want_count:
+        count = torch.empty((ngroups, m), dtype=torch.int64, device=dev)
+        c.out_count = count.data_ptr()
+    c.stream = torch.cuda.current_stream(dev).cuda_stream
+    _ffi.check(lib.fh_grouped_quantile_cols(ctypes.byref(c), nq, int(max_seg_rows)))
+    for t in (values2d, codes_sorted, perm, q_t, out, count):
+        _record(t, torch.cuda.current_stream(dev))
+    return (out, count) if want_count else out
+
+
+def grouped_quantile_cols(
+    values2d: torch.Tensor,
+    codes_sorted: torch.Tensor,
+    perm: torch.Tensor,
+    ngroups: int,
+    q,
+    *,
+    skipnan: bool = False,
+    max_seg_rows: int,
+    want_count: bool = False,
+):
+    """Grouped linear-interpolation quantiles over the LEADING axis of a 2-D
+    array (n_t, m) with column stride 1, each group's rows sorted in LDS
+    (fh_grouped_quantile_cols). codes_sorted/perm as grouped_partials_cols
+    takes them; max_seg_rows bounds every group's row count and must be
+    within _ffi.quantile_cols_max_rows. Returns f64 (nq, ngroups, m), equal to
+    grouped_quantile column by column; with want_count also the int64
+    (ngroups, m) non-NaN row counts."""
+    q_t = torch.as_tensor(
+        np.atleast_1d(np.asarray(q, dtype=np.float64)), device=values2d.device
+    ).contiguous()
+    return _sorted_cols(values2d, codes_sorted, perm, ngroups, q_t, skipnan=skipnan,
+                        max_seg_rows=max_seg_rows, want_count=want_count)
+
+
+def grouped_mode_cols(
+    values2d: torch.Tensor,
+    codes_sorted: torch.Tensor,
+    perm: torch.Tensor,
+    ngroups: int,
+    *,
+    skipnan: bool = False,
+    max_seg_rows: int,
+    want_count: bool = False,
+):
+    """Grouped mode over the leading axis of a 2-D array, grouped_mode's rules
+    column by column (-0.0 counts as +0.0: the kernel folds it while staging,
+    no copy of the values is made). Returns values-dtype (ngroups, m); with
+    want_count also the int64 (ngroups, m) non-NaN row counts."""
+    return _sorted_cols(values2d, codes_sorted, perm, ngroups, None, skipnan=skipnan,
+                        max_seg_rows=max_seg_rows, want_count=want_count)
+
+
 def var_partials(
     group_idx, array, *, skipnan, size, labels2=None, grp_shape=None,
     global_counts=None, global_sums=None,

@@ -63,6 +63,11 @@ _LEAD_FOLD_FUNCS = _QUANTILE_FUNCS + ("mode", "nanmode") + _ARG_FUNCS + _FIRST_L
 # (_cols_order_ok) instead of the lead fold
 COLS_ORDER_FUNCS = True
 _COLS_ORDER = _ARG_FUNCS + _FIRST_LAST_FUNCS
+# options.cols_sorted_funcs: the quantile family and mode over leading dims
+# sort each group's rows in LDS (fh_grouped_quantile_cols) where the call is
+# eligible (_cols_sorted_ok) instead of the lead fold
+COLS_SORTED_FUNCS = True
+_COLS_SORTED = _QUANTILE_FUNCS + ("mode", "nanmode")
 
 _TORCH_TO_NP = {
     torch.float32: np.dtype("float32"),
@@ -804,7 +809,7 @@ class _Plan:
         "min_count_", "fill_value", "out_dtype",
         # _select_engine, _fold_lead
         "label_src", "row_offset", "cols", "many_served", "lead_folded",
-        "arg_localize_N", "base_ngroups", "cols_order",
+        "arg_localize_N", "base_ngroups", "cols_order", "cols_sorted_rows",
     )
 
 
@@ -997,12 +1002,44 @@ def _cols_order_ok(p, vt):
     )
 
 
+def _cols_sorted_ok(p, vt):
+    """Whether a quantile-family or mode call over leading dims takes the
+    sort-in-LDS column form; sets p.cols_sorted_rows (the largest group's row
+    count) when it does. Where a condition fails the call keeps the lead fold
+    with its results and exceptions. The largest group is read from the
+    sorted codes on the host, the copy grouped_partials_cols also makes for
+    its chunk plan: a stream under capture cannot, and keeps the fold."""
+    if not (
+        COLS_SORTED_FUNCS
+        and p.func in _COLS_SORTED
+        and vt.dtype in _TORCH_VDTYPE
+        and not p.dist_on
+        and p.inp.dt_dtype is None
+        and p.subset_keep_shape is None
+        and vt.numel() > 0 and p.ngroups > 0
+        and not (vt.is_cuda and torch.cuda.is_current_stream_capturing())
+    ):
+        return False
+    cap = _ffi.quantile_cols_max_rows(_TORCH_VDTYPE[vt.dtype])
+    if cap <= 0:
+        return False
+    sc = p.cols[1].cpu().numpy()
+    sc = sc[np.searchsorted(sc, 0):]  # rows of code -1 sort first
+    edges = np.flatnonzero(np.diff(sc)) + 1
+    longest = int(np.diff(np.concatenate(([0], edges, [sc.size]))).max()) if sc.size else 1
+    if longest > cap:
+        return False
+    p.cols_sorted_rows = longest
+    return True
+
+
 def _select_engine(p, by):
     """1-D, column (either summary-served inside an eligible
     groupby_reduce_many), or lead-folded. Fills in the plan's engine fields;
     the lead fold (_fold_lead) also rewrites its vals, labels and ngroups."""
     p.label_src, p.row_offset, p.cols = None, p.shard_row_offset, None
     p.many_served = p.lead_folded = p.cols_order = False
+    p.cols_sorted_rows = None
     many, facs = p.many, p.facs
     if p.lead_M == 1:
         # label-code cache key: the CALLER's by object(s) — `labels` is a
@@ -1061,6 +1098,11 @@ def _select_engine(p, by):
         # groupby_reduce_many these names share the factorization only.
         p.cols_order = True
         return _EngineCols(p)
+    if _cols_sorted_ok(p, vt):
+        # each group's rows sorted in LDS: no composite labels, no flattened
+        # copy, no device-wide sort, no limit on N * lead_M. Inside
+        # groupby_reduce_many these names share the factorization only.
+        return _EngineCols(p)
     # (the column view and the sort above go unused here: kept, since
     # dropping them would change which kernels these calls launch)
     _fold_lead(p, codes_full, N)
@@ -1075,18 +1117,73 @@ _FINISHED = object()
 _I64_MAX = (1 << 63) - 1
 
 
-def _family_quantile(p, eng):
-    from .aggregate_hip import grouped_quantile
-
-    func, vals, ngroups = p.func, p.vals, p.ngroups
-    if func in ("quantile", "nanquantile"):
+def _quantile_q(p):
+    """(q as f64[nq], whether the caller's q was a scalar)."""
+    if p.func in ("quantile", "nanquantile"):
         if not p.finalize_kwargs or "q" not in p.finalize_kwargs:
             raise ValueError("Please pass `q` for quantile calculations.")
         q = p.finalize_kwargs["q"]
     else:
         q = 0.5
-    q_arr = np.atleast_1d(np.asarray(q, dtype=np.float64))
-    scalar_q = np.isscalar(q) or np.ndim(q) == 0
+    return np.atleast_1d(np.asarray(q, dtype=np.float64)), np.isscalar(q) or np.ndim(q) == 0
+
+
+def _quantile_finish(p, resq, scalar_q, nq, counts):
+    """The quantile family's own fill rule: NaN already marks empty groups,
+    so only an explicit fill under min_count writes anything. counts is a
+    callable: the pass is made only where the rule needs it."""
+    result = resq[0] if scalar_q else resq
+    if p.min_count_ > 0:
+        counts = counts()
+        if p.fill_value is not None:
+            mask = counts < p.min_count_
+            fv = torch.tensor(float(p.fill_value), dtype=result.dtype, device=p.device)
+            result = torch.where(mask, fv, result)
+    if not scalar_q:
+        p.out_prefix = (nq,)
+    return result.to(_torch_dtype(p.out_dtype)), _FINISHED, None
+
+
+def _family_quantile_cols(p, eng):
+    """Quantiles over leading dims, sorted in LDS: (nq, ngroups, M) from one
+    read of the (N, lead_M) view; the kernel's non-NaN counts stand in for
+    the SET_COUNT pass of the min_count rule."""
+    from .aggregate_hip import grouped_quantile_cols
+
+    q_arr, scalar_q = _quantile_q(p)
+    vt, scodes, perm = p.cols
+    want = p.min_count_ > 0
+    r = grouped_quantile_cols(
+        vt, scodes, perm, p.ngroups, q_arr, skipnan=p.agg.skipnan,
+        max_seg_rows=p.cols_sorted_rows, want_count=want,
+    )
+    resq, counts = r if want else (r, None)
+    return _quantile_finish(p, resq, scalar_q, len(q_arr), lambda: counts)
+
+
+def _family_mode_cols(p, eng):
+    """Mode over leading dims, sorted in LDS; the counts _family_mode takes
+    from a SET_COUNT pass come from the same kernel."""
+    from .aggregate_hip import grouped_mode_cols
+
+    vt, scodes, perm = p.cols
+    result, counts = grouped_mode_cols(
+        vt, scodes, perm, p.ngroups, skipnan=p.agg.skipnan,
+        max_seg_rows=p.cols_sorted_rows, want_count=True,
+    )
+    empty_mask = (
+        torch.zeros_like(counts, dtype=torch.bool)
+        if p.arr.dtype.is_floating_point
+        else counts == 0
+    )
+    return result, empty_mask, counts
+
+
+def _family_quantile(p, eng):
+    from .aggregate_hip import grouped_quantile
+
+    vals, ngroups = p.vals, p.ngroups
+    q_arr, scalar_q = _quantile_q(p)
     if vals.numel() == 0 and not p.dist_on:
         resq = torch.full((len(q_arr), ngroups), float("nan"), dtype=torch.float64, device=p.device)
     elif p.dist_on:
@@ -1101,18 +1198,7 @@ def _family_quantile(p, eng):
             vals, p.labels, ngroups, q_arr, skipnan=p.agg.skipnan,
             labels2=p.labels2, grp_shape=p.grp_pair,
         )
-    result = resq[0] if scalar_q else resq
-    # its own fill rule: NaN already marks empty groups, so only an explicit
-    # fill under min_count writes anything
-    if p.min_count_ > 0:
-        counts = eng.count()
-        if p.fill_value is not None:
-            mask = counts < p.min_count_
-            fv = torch.tensor(float(p.fill_value), dtype=result.dtype, device=p.device)
-            result = torch.where(mask, fv, result)
-    if not scalar_q:
-        p.out_prefix = (len(q_arr),)
-    return result.to(_torch_dtype(p.out_dtype)), _FINISHED, None
+    return _quantile_finish(p, resq, scalar_q, len(q_arr), eng.count)
 
 
 def _family_mode(p, eng):
@@ -1418,9 +1504,9 @@ def _family_simple(p, eng):
 def _select_family(p):
     func = p.func
     if func in _QUANTILE_FUNCS:
-        return _family_quantile
+        return _family_quantile if p.cols_sorted_rows is None else _family_quantile_cols
     if func in ("mode", "nanmode"):
-        return _family_mode
+        return _family_mode if p.cols_sorted_rows is None else _family_mode_cols
     if p.cols_order:
         return _family_arg_cols if func in _ARG_FUNCS else _family_first_last_cols
     if func in _ARG_FUNCS:
@@ -1475,9 +1561,11 @@ def _shape_and_order(p, result):
     first-appearance order."""
     many = p.many
     if p.lead_M > 1 and not p.lead_folded:
-        # column partials are (ngroups, M) group-major; the API result puts
-        # the group dims last
-        result = result.reshape(p.ngroups, p.lead_M).t().contiguous()
+        # column partials are (q..., ngroups, M) group-major; the API result
+        # puts the group dims last
+        result = result.reshape(
+            p.out_prefix + (p.ngroups, p.lead_M)
+        ).transpose(-1, -2).contiguous()
     result = result.reshape(
         p.out_prefix + p.lead_shape + (p.subset_keep_shape or ()) + p.grp_shape
     )

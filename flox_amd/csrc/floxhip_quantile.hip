@@ -21,6 +21,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/floxhip.h"
+#include "../../include/floxhip_qcols.h"
 
 #define FHQ_CHECK(x)                                \
   do {                                              \
@@ -129,104 +130,93 @@ __global__ void k_qoffsets(const uint64_t* __restrict__ keys,
   off[g] = lo;
 }
 
-/* numpy method="linear" quantile per (group, q); reference _lerp
- * (aggregate_flox.py:26-47) including the t>=0.5 form */
-template <typename V, bool PACKED>
-__global__ void k_quantile(const uint64_t* __restrict__ keys, int64_t n,
-                           const int64_t* __restrict__ off, int64_t ngroups,
-                           const double* __restrict__ q, int nq, int skipna,
-                           double* __restrict__ out) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= ngroups * nq) return;
-  const int64_t g = t % ngroups;
-  const int qi = (int)(t / ngroups);
-  const int64_t start = off[g], end = off[g + 1];
-  const int64_t full = end - start;
-  const double NAN_ = __longlong_as_double(0x7FF8000000000000ll);
-  double res = NAN_;
-  const bool is_f = std::is_same<V, float>::value || std::is_same<V, double>::value;
+/* ---- selection rules over one group's ascending keys ---------------------
+ * Shared by the 1-D kernels (keys in global memory after the radix sort) and
+ * the column kernel (keys in LDS after the bitonic sort). `key_at(k)` returns
+ * the encoded value at position k of the group's run, 0 <= k < full: the
+ * enc32 / enc64 form of the value alone, without the group code. */
+template <typename V>
+using qkey_t = typename std::conditional<sizeof(V) == 4, uint32_t, uint64_t>::type;
+
+template <typename V>
+constexpr bool is_float_v = std::is_same<V, float>::value || std::is_same<V, double>::value;
+
+template <typename V>
+__device__ __forceinline__ qkey_t<V> enc_key(V v) {
+  if constexpr (std::is_same<V, float>::value) return enc32f(v);
+  else if constexpr (std::is_same<V, int32_t>::value) return enc32i(v);
+  else if constexpr (std::is_same<V, double>::value) return enc64f(v);
+  else return enc64i(v);
+}
+template <typename V>
+__device__ __forceinline__ V dec_key(qkey_t<V> e) {
+  if constexpr (std::is_same<V, float>::value) return dec32f(e);
+  else if constexpr (std::is_same<V, int32_t>::value) return dec32i(e);
+  else if constexpr (std::is_same<V, double>::value) return dec64f(e);
+  else return dec64i(e);
+}
+
+/* rows before the first canonical NaN (they sort last within the run) */
+template <typename V, typename KeyAt>
+__device__ __forceinline__ int64_t sorted_nonnan(KeyAt key_at, int64_t full) {
+  if (!is_float_v<V>) return full;
+  const qkey_t<V> nan_key = ~(qkey_t<V>)0;
+  int64_t lo = 0, hi = full;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (key_at(mid) < nan_key)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+/* numpy method="linear" quantile; reference _lerp (aggregate_flox.py:26-47)
+ * including the t>=0.5 form. NaN for an empty group, an all-NaN group, and a
+ * NaN-containing group without skipna. actual = sorted_nonnan(key_at, full). */
+template <typename V, typename KeyAt>
+__device__ __forceinline__ double quantile_of_sorted(KeyAt key_at, int64_t full,
+                                                     int64_t actual, double q, int skipna) {
+  double res = __longlong_as_double(0x7FF8000000000000ll);
   if (full > 0) {
-    int64_t nan_start = end;
-    if (is_f) {
-      /* canonical NaNs sort last within the run */
-      int64_t lo = start, hi = end;
-      const uint64_t nan_key = PACKED ? ((((uint64_t)(uint32_t)g) << 32) | 0xFFFFFFFFu) : ~0ull;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (keys[mid] < nan_key)
-          lo = mid + 1;
-        else
-          hi = mid;
-      }
-      nan_start = lo;
-    }
-    const int64_t actual = nan_start - start;
     const bool nanmask = actual != full;
     if (actual > 0 && (skipna || !nanmask)) {
-      const double vi = q[qi] * (double)(actual - 1);
+      const double vi = q * (double)(actual - 1);
       int64_t lo_i = (int64_t)floor(vi), hi_i = (int64_t)ceil(vi);
+      /* q in [0, 1] needs only the first and the last clamp; the other two
+       * keep a q outside it inside the run */
       if (lo_i < 0) lo_i = 0;
+      if (lo_i > actual - 1) lo_i = actual - 1;
+      if (hi_i < 0) hi_i = 0;
       if (hi_i > actual - 1) hi_i = actual - 1;
-      auto val_at = [&](int64_t k) -> double {
-        const uint64_t key = keys[start + k];
-        if (PACKED) {
-          const uint32_t e = (uint32_t)key;
-          if (std::is_same<V, float>::value) return (double)dec32f(e);
-          return (double)dec32i(e);
-        }
-        if (std::is_same<V, double>::value) return dec64f(key);
-        return (double)dec64i(key);
-      };
-      const double a = val_at(lo_i), b = val_at(hi_i);
+      const double a = (double)dec_key<V>(key_at(lo_i));
+      const double b = (double)dec_key<V>(key_at(hi_i));
       const double tq = vi - (double)lo_i;
       const double diff = b - a;
       res = (tq >= 0.5) ? (b - diff * (1.0 - tq)) : (a + diff * tq);
     }
   }
-  out[(int64_t)qi * ngroups + g] = res;
+  return res;
 }
 
-/* mode: longest equal-value run in each group's sorted span; sorted order
- * makes scipy's tie rule (smallest of the modes) the first-found run.
- * nan_policy: "propagate" (mode) -> NaN result when the group has NaNs;
- * "omit" (nanmode) -> NaN tail ignored (reference aggregate_npg.py:185-215). */
-template <typename V, bool PACKED>
-__global__ void k_mode(const uint64_t* __restrict__ keys, int64_t n,
-                       const int64_t* __restrict__ off, int64_t ngroups,
-                       int skipna, V* __restrict__ out) {
-  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= ngroups) return;
-  const int64_t start = off[g], end = off[g + 1];
-  const bool is_f = std::is_same<V, float>::value || std::is_same<V, double>::value;
-  const double NAN_ = __longlong_as_double(0x7FF8000000000000ll);
-  auto write_nan_or_zero = [&]() { out[g] = is_f ? (V)NAN_ : (V)0; };
-  if (end <= start) {
-    write_nan_or_zero();
-    return;
-  }
-  int64_t nan_start = end;
-  if (is_f) {
-    int64_t lo = start, hi = end;
-    const uint64_t nan_key = PACKED ? ((((uint64_t)(uint32_t)g) << 32) | 0xFFFFFFFFu) : ~0ull;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (keys[mid] < nan_key)
-        lo = mid + 1;
-      else
-        hi = mid;
-    }
-    nan_start = lo;
-  }
-  if (nan_start == start) {
-    /* no non-NaN values: NaN either way (scipy omit warns and returns NaN;
-     * propagate's most-common value IS NaN) */
-    write_nan_or_zero();
-    return;
-  }
-  uint64_t best = keys[start], cur = keys[start];
+/* mode: longest equal-value run in the sorted span; sorted order makes
+ * scipy's tie rule (smallest of the modes) the first-found run.
+ * nan_policy: "propagate" (mode) -> NaN result when NaNs are strictly the
+ * most frequent value; "omit" (nanmode) -> NaN tail ignored (reference
+ * aggregate_npg.py:185-215). Empty and all-NaN groups give NaN (0 for
+ * integer dtypes): scipy omit warns and returns NaN; propagate's most-common
+ * value IS NaN. */
+template <typename V, typename KeyAt>
+__device__ __forceinline__ V mode_of_sorted(KeyAt key_at, int64_t full, int64_t actual,
+                                            int skipna) {
+  const V nan_or_zero =
+      is_float_v<V> ? (V)__longlong_as_double(0x7FF8000000000000ll) : (V)0;
+  if (full <= 0 || actual == 0) return nan_or_zero;
+  qkey_t<V> best = key_at(0), cur = best;
   int64_t best_n = 1, cur_n = 1;
-  for (int64_t i = start + 1; i < nan_start; ++i) {
-    const uint64_t k = keys[i];
+  for (int64_t i = 1; i < actual; ++i) {
+    const qkey_t<V> k = key_at(i);
     if (k == cur) {
       ++cur_n;
     } else {
@@ -242,24 +232,177 @@ __global__ void k_mode(const uint64_t* __restrict__ keys, int64_t n,
     best = cur;
     best_n = cur_n;
   }
-  if (!skipna && (end - nan_start) > best_n) {
-    /* scipy propagate counts NaNs as a value: a strictly-most-frequent NaN
-     * run wins (ties resolve to the smallest, i.e. any non-NaN) */
-    write_nan_or_zero();
-    return;
-  }
-  if (PACKED) {
-    const uint32_t e = (uint32_t)best;
-    if (std::is_same<V, float>::value)
-      out[g] = (V)dec32f(e);
+  /* scipy propagate counts NaNs as a value: a strictly-most-frequent NaN run
+   * wins (ties resolve to the smallest, i.e. any non-NaN) */
+  if (!skipna && (full - actual) > best_n) return nan_or_zero;
+  return dec_key<V>(best);
+}
+
+template <typename V, bool PACKED>
+__global__ void k_quantile(const uint64_t* __restrict__ keys, int64_t n,
+                           const int64_t* __restrict__ off, int64_t ngroups,
+                           const double* __restrict__ q, int nq, int skipna,
+                           double* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= ngroups * nq) return;
+  const int64_t g = t % ngroups;
+  const int qi = (int)(t / ngroups);
+  const int64_t start = off[g], full = off[g + 1] - start;
+  /* a packed key carries the group code above the value: drop it */
+  auto key_at = [&](int64_t k) { return (qkey_t<V>)keys[start + k]; };
+  const int64_t actual = full > 0 ? sorted_nonnan<V>(key_at, full) : 0;
+  out[(int64_t)qi * ngroups + g] = quantile_of_sorted<V>(key_at, full, actual, q[qi], skipna);
+}
+
+template <typename V, bool PACKED>
+__global__ void k_mode(const uint64_t* __restrict__ keys, int64_t n,
+                       const int64_t* __restrict__ off, int64_t ngroups,
+                       int skipna, V* __restrict__ out) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= ngroups) return;
+  const int64_t start = off[g], full = off[g + 1] - start;
+  auto key_at = [&](int64_t k) { return (qkey_t<V>)keys[start + k]; };
+  const int64_t actual = full > 0 ? sorted_nonnan<V>(key_at, full) : 0;
+  out[g] = mode_of_sorted<V>(key_at, full, actual, skipna);
+}
+
+/* ---- column form: sort each group's segment in LDS ----------------------
+ * One workgroup per (column tile, group); the tile index runs fastest, so
+ * neighbouring workgroups read neighbouring pieces of the same rows. The
+ * workgroup finds its segment of the sorted codes by binary search, stages
+ * the segment's rows for C = 1 << logC columns as keys [row][column] in
+ * dynamic LDS (lanes along columns: one row of the tile per request), sorts
+ * every column with a bitonic network whose compare-exchange steps take
+ * (pair, column) with the column fastest, and evaluates the rules above on
+ * the sorted keys. The network is as wide as the next power of two above the
+ * segment found, never wider than P; slots past the segment hold the
+ * all-ones key, which sorts last (for floats it is the canonical NaN, for
+ * integers the dtype's maximum: either way positions below the segment's
+ * length hold the segment's own values). A segment longer than P rows is cut
+ * at P: memory-safe, that group's result is unspecified.
+ * MODE folds -0.0 into +0.0 while staging (scipy counts by numeric
+ * equality; the two encodings differ). */
+template <typename V, bool MODE>
+__global__ __launch_bounds__(1024) void k_sortsel_cols(
+    const V* __restrict__ values, const int32_t* __restrict__ codes,
+    const int32_t* __restrict__ perm, int64_t n, int64_t m, int64_t ldm,
+    int64_t ngroups, int64_t g_base, int64_t ntiles, int P, int logC,
+    const double* __restrict__ q, int nq, int skipna, void* __restrict__ out,
+    int64_t* __restrict__ out_count) {
+  using K = qkey_t<V>;
+  extern __shared__ __align__(16) unsigned char qcols_lds[];
+  K* s = reinterpret_cast<K*>(qcols_lds);
+  const int C = 1 << logC;
+  const int64_t g = g_base + (int64_t)blockIdx.x / ntiles;
+  const int64_t c0 = ((int64_t)blockIdx.x % ntiles) << logC;
+  if (g >= ngroups) return;
+  const int tid = threadIdx.x, nthr = blockDim.x;
+
+  /* segment [start, start + len) of code g; rows of code -1 sort first */
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((int64_t)codes[mid] < g)
+      lo = mid + 1;
     else
-      out[g] = (V)dec32i((int32_t)e);
-  } else {
-    if (std::is_same<V, double>::value)
-      out[g] = (V)dec64f(best);
-    else
-      out[g] = (V)dec64i(best);
+      hi = mid;
   }
+  const int64_t start = lo;
+  hi = start + P < n ? start + P : n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((int64_t)codes[mid] <= g)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  const int len = (int)(lo - start); /* <= P */
+  int W = 1;
+  while (W < len) W <<= 1; /* <= P: P is a power of two >= len */
+
+  if (len > 0) {
+    const int c = tid & (C - 1);
+    const bool col_ok = c0 + c < m;
+    const int rstep = nthr >> logC;
+#pragma unroll 4
+    for (int r = tid >> logC; r < W; r += rstep) {
+      K key = ~(K)0;
+      if (r < len && col_ok) {
+        V v = values[(int64_t)perm[start + r] * ldm + c0 + c];
+        if (MODE && is_float_v<V>) {
+          if (v == (V)0) v = (V)0;
+        }
+        key = enc_key<V>(v);
+      }
+      s[(r << logC) + c] = key;
+    }
+    __syncthreads();
+    const int npairs = (W >> 1) << logC;
+    for (int k = 2; k <= W; k <<= 1) {
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int t = tid; t < npairs; t += nthr) {
+          const int cc = t & (C - 1), pi = t >> logC;
+          const int i = ((pi & ~(j - 1)) << 1) | (pi & (j - 1));
+          const int ia = (i << logC) + cc, ib = ((i | j) << logC) + cc;
+          const K a = s[ia], b = s[ib];
+          if ((i & k) == 0 ? a > b : a < b) {
+            s[ia] = b;
+            s[ib] = a;
+          }
+        }
+        __syncthreads();
+      }
+    }
+  }
+
+  const int nsel = MODE ? C : (nq << logC);
+  for (int t = tid; t < nsel; t += nthr) {
+    const int cc = t & (C - 1), qi = t >> logC;
+    const int64_t col = c0 + cc;
+    if (col >= m) continue;
+    auto key_at = [&](int64_t k) { return s[((int)k << logC) + cc]; };
+    const int64_t actual = len > 0 ? sorted_nonnan<V>(key_at, len) : 0;
+    if (MODE)
+      ((V*)out)[g * m + col] = mode_of_sorted<V>(key_at, len, actual, skipna);
+    else
+      ((double*)out)[((int64_t)qi * ngroups + g) * m + col] =
+          quantile_of_sorted<V>(key_at, len, actual, q[qi], skipna);
+    if (out_count && qi == 0) out_count[g * m + col] = actual;
+  }
+}
+
+template <typename V, bool MODE>
+int launch_sortsel_cols(fh_call* c, int nq, const fh_qcols_plan& pl) {
+  auto kern = k_sortsel_cols<V, MODE>;
+  if (pl.lds_bytes > 64 * 1024)
+    FHQ_CHECK(hipFuncSetAttribute((const void*)kern,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)pl.lds_bytes));
+  const int64_t ntiles = (c->m + pl.C - 1) / pl.C;
+  /* the grid is one-dimensional (no 65535 cap on groups): launch in slices
+   * of groups where tiles x groups passes 2^31 - 1 */
+  const int64_t gstep = std::max<int64_t>(1, (int64_t)0x7FFFFFFF / ntiles);
+  for (int64_t g0 = 0; g0 < c->ngroups; g0 += gstep) {
+    const int64_t ng = std::min<int64_t>(gstep, c->ngroups - g0);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(ng * ntiles)), dim3(pl.block),
+                       (size_t)pl.lds_bytes, (hipStream_t)c->stream,
+                       (const V*)c->values, (const int32_t*)c->labels,
+                       (const int32_t*)c->perm, c->n, c->m, c->ldm, c->ngroups, g0,
+                       ntiles, (int)pl.P, pl.logC, c->means, nq,
+                       (c->flags & FH_SKIPNAN) ? 1 : 0, c->out_sum, c->out_count);
+    FHQ_CHECK(hipGetLastError());
+  }
+  return 0;
+}
+
+template <typename V>
+int run_quantile_cols(fh_call* c, int nq, int64_t max_seg_rows) {
+  fh_qcols_plan pl;
+  if (!fh_qcols_plan_for(max_seg_rows < 1 ? 1 : max_seg_rows, (int)sizeof(V), &pl)) return 20;
+  c->path_used = 3;
+  if (c->ngroups == 0 || c->m == 0) return 0;
+  return nq == 0 ? launch_sortsel_cols<V, true>(c, nq, pl)
+                 : launch_sortsel_cols<V, false>(c, nq, pl);
 }
 
 template <typename V, typename L>
@@ -397,6 +540,33 @@ int fh_grouped_quantile(fh_call* c, int nq) {
                                    : run_quantile<int32_t, int32_t>(c, q_dev, nq, out);
     default:
       return 9;
+  }
+}
+
+/* column form (include/floxhip.h): sort each group's rows in LDS */
+int64_t fh_quantile_cols_max_rows(int vdtype) {
+  switch (vdtype) {
+    case FH_F32:
+    case FH_I32:
+      return fh_qcols_capacity(4);
+    case FH_F64:
+    case FH_I64:
+      return fh_qcols_capacity(8);
+    default:
+      return 0;
+  }
+}
+
+int fh_grouped_quantile_cols(fh_call* c, int nq, int64_t max_seg_rows) {
+  if (!c || !c->values || !c->labels || !c->perm || !c->out_sum) return 21;
+  if (nq < 0 || (nq > 0 && !c->means)) return 21;
+  if (c->n < 0 || c->m < 0 || c->ngroups < 0 || c->n >= (1LL << 31)) return 21;
+  switch (c->vdtype) {
+    case FH_F32: return run_quantile_cols<float>(c, nq, max_seg_rows);
+    case FH_F64: return run_quantile_cols<double>(c, nq, max_seg_rows);
+    case FH_I64: return run_quantile_cols<int64_t>(c, nq, max_seg_rows);
+    case FH_I32: return run_quantile_cols<int32_t>(c, nq, max_seg_rows);
+    default: return 9;
   }
 }
 

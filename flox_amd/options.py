@@ -32,6 +32,14 @@ Supported options:
       at any size, where the call is eligible: f32/f64/i32/i64 values after
       normalisation, not distributed, no datetime values, no axis subset,
       at least one row and one group (core.py).
+  cols_sorted_funcs: False sends quantile/nanquantile/median/nanmedian and
+      mode/nanmode over leading dims through the lead fold (a device-wide
+      radix sort of N * lead_M composite keys, limited to N * lead_M <
+      2**31); on (the default) each group's rows are sorted in LDS by the
+      column kernel, which reads the caller's strided view in place, once,
+      at any size, where the call is eligible: the conditions of
+      cols_order_funcs, no hipGraph capture, and no group longer than the
+      kernel's capacity (2048 rows) (core.py).
 """
 
 from __future__ import annotations
@@ -49,6 +57,7 @@ OPTIONS = {
     "fused_finalize": None,           # None = on
     "fused_many": None,               # None = on
     "cols_order_funcs": None,         # None = on
+    "cols_sorted_funcs": None,        # None = on
 }
 
 _CACHE_FIELDS = {
@@ -92,6 +101,11 @@ def _apply(name, value):
         if value is not None:
             core.COLS_ORDER_FUNCS = bool(value)
         return ("cols_order_funcs", old)
+    if name == "cols_sorted_funcs":
+        old = core.COLS_SORTED_FUNCS
+        if value is not None:
+            core.COLS_SORTED_FUNCS = bool(value)
+        return ("cols_sorted_funcs", old)
     if name == "sparse_combine_ngroups":
         old = distributed.SPARSE_NGROUPS
         if value is not None:
@@ -122,6 +136,8 @@ def _restore(name, old):
         core.FUSED_MANY = old
     elif name == "cols_order_funcs":
         core.COLS_ORDER_FUNCS = old
+    elif name == "cols_sorted_funcs":
+        core.COLS_SORTED_FUNCS = old
     elif name == "sparse_combine_ngroups":
         distributed.SPARSE_NGROUPS = old
     elif name == "sparse_combine_fraction":

@@ -272,6 +272,32 @@ int fh_grouped_reduce_cols(fh_call* c);
  * FH_SET_IDXMIN/IDXMAX and FH_SET_ARG*_COLS lack the symbol. */
 int fh_cols_supports(int op_set);
 
+/* grouped quantiles / mode over the leading axis of a multi-column array:
+ * the column form of fh_grouped_quantile. Inputs as fh_grouped_reduce_cols
+ * (values n x m with row stride ldm, labels = int32 codes in [-1, ngroups)
+ * sorted ascending, perm = the int32 sorting permutation, any perm that sorts
+ * the codes); `means` carries the device q array (f64[nq]) as it does for
+ * fh_grouped_quantile; FH_SKIPNAN in flags. max_seg_rows is the caller's
+ * upper bound on any group's row count: one workgroup stages one group's
+ * rows for a tile of columns in LDS, sorts them there and answers every q
+ * (include/floxhip_qcols.h has the tile plan), so the values are read once,
+ * in place, with no scratch, no host sync and no limit on n * m. A group
+ * longer than max_seg_rows gets an unspecified result (memory-safe).
+ * Outputs: nq > 0: out_sum = f64 [nq][ngroups][m]; nq == 0 (mode): out_sum =
+ * value dtype [ngroups][m]; out_count (nullable) = int64 [ngroups][m] non-NaN
+ * rows of each (group, column). Results equal fh_grouped_quantile's bit for
+ * bit (the same selection rules run on the sorted keys); mode treats -0.0 as
+ * +0.0. path_used = 3. Errors (no launch, outputs untouched): 20 =
+ * max_seg_rows beyond fh_quantile_cols_max_rows(vdtype); 21 = a missing
+ * buffer (values, labels, perm, out_sum, or means with nq > 0) or a negative
+ * / out-of-int32 extent; 9 = unknown value dtype. fh_error_string predates
+ * codes 20 and 21. Came without a new revision (fh_call is unchanged): a
+ * caller detects it by the symbol. */
+int fh_grouped_quantile_cols(fh_call* c, int nq, int64_t max_seg_rows);
+/* the longest segment fh_grouped_quantile_cols can stage for this value
+ * dtype (2048 for all four); 0 for an unknown dtype */
+int64_t fh_quantile_cols_max_rows(int vdtype);
+
 /* pack (order-preserving 32-bit value encoding, global row index) into one
  * int64 key per row, so that a grouped MIN over the keys is argmin/argmax
  * with np.argmin's first-occurrence tie-break (the packed form of the
