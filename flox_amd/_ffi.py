@@ -163,8 +163,19 @@ def load_library():
         lib.fh_grouped_quantile_cols.restype = ctypes.c_int
         lib.fh_quantile_cols_max_rows.argtypes = [ctypes.c_int]
         lib.fh_quantile_cols_max_rows.restype = ctypes.c_int64
+    # and the column form of the grouped scans
+    if hasattr(lib, "fh_grouped_scan_cols"):
+        lib.fh_grouped_scan_cols.argtypes = [
+            ctypes.POINTER(FhCall), ctypes.c_int, ctypes.c_int64,
+        ]
+        lib.fh_grouped_scan_cols.restype = ctypes.c_int
     _lib = lib
     return lib
+
+
+def has_scan_cols() -> bool:
+    """Whether the loaded library has fh_grouped_scan_cols."""
+    return hasattr(load_library(), "fh_grouped_scan_cols")
 
 
 def quantile_cols_max_rows(vdtype: int) -> int:
@@ -194,6 +205,12 @@ _QCOLS_ERRORS = {
     20: "max_seg_rows exceeds fh_quantile_cols_max_rows for the value dtype",
     21: "fh_grouped_quantile_cols: missing values/labels/perm/out_sum buffer, "
         "missing q array, or an extent that is negative or beyond int32 rows",
+    # fh_grouped_scan_cols
+    22: "fh_grouped_scan_cols: missing values/labels/perm/out_sum buffer",
+    23: "fh_grouped_scan_cols: an extent that is negative, beyond int32 rows, "
+        "a row stride below the column count, or nchunks out of range",
+    24: "fh_grouped_scan_cols: unknown op, or a value dtype the op is not "
+        "served for (sums: f32/f64/i64, fills: f32/f64)",
 }
 
 

@@ -823,6 +823,80 @@ def grouped_mode_cols(
                         max_seg_rows=max_seg_rows, want_count=want_count)
 
 
+_SCAN_COLS_OPS = {"cumsum": 0, "nancumsum": 1, "ffill": 2, "bfill": 3}
+
+
+def grouped_scan_cols(
+    values2d: torch.Tensor,
+    codes_sorted: torch.Tensor,
+    perm: torch.Tensor,
+    func: str,
+    out: torch.Tensor | None = None,
+) -> torch.Tensor:
+    """Grouped scan over the LEADING axis of a 2-D array (n_t, m) with column
+    stride 1 (fh_grouped_scan_cols): cumsum / nancumsum for f32, f64 and i64,
+    ffill / bfill for f32 and f64. codes_sorted/perm: int32 tensors from a
+    STABLE sort of the per-row group codes, as grouped_partials_cols takes
+    them; a scan depends on the row order inside a group, so the sort must be
+    stable. Every run of equal codes scans as one group, the -1 run included.
+    The values are read in place and the result is written once: `out`, where
+    given, is an (n_t, m) tensor of the values' dtype with column stride 1 and
+    any row stride, not overlapping the values; else a contiguous one is
+    allocated. Returns the (n_t, m) result."""
+    lib = _ffi.load_library()
+    if not hasattr(lib, "fh_grouped_scan_cols"):
+        raise RuntimeError("libfloxhip.so lacks fh_grouped_scan_cols: rebuild the extension")
+    _require_gpu_tensor(values2d, "values")
+    assert values2d.ndim == 2 and (values2d.stride(1) == 1 or values2d.shape[1] <= 1)
+    assert codes_sorted.dtype == torch.int32 and perm.dtype == torch.int32
+    if values2d.dtype not in _TORCH_VDTYPE:
+        raise NotImplementedError(f"engine=hip does not support values dtype {values2d.dtype}")
+    n_t, m = values2d.shape
+    dev = values2d.device
+    if out is None:
+        out = torch.empty((n_t, m), dtype=values2d.dtype, device=dev)
+    assert out.shape == values2d.shape and out.dtype == values2d.dtype and out.device == dev
+    assert out.stride(1) == 1 or m <= 1
+
+    c = FhCall()
+    c.vdtype = _TORCH_VDTYPE[values2d.dtype]
+    c.ldtype = _ffi.L_I32
+    c.n = n_t
+    c.m = m
+    c.ldm = values2d.stride(0)
+    c.values = values2d.data_ptr()
+    codes_sorted = codes_sorted.contiguous()
+    perm = perm.contiguous()
+    c.labels = codes_sorted.data_ptr()
+    c.perm = perm.data_ptr()
+    c.out_sum = out.data_ptr()
+    # group-aligned row chunks, as grouped_partials_cols plans them: the grid
+    # is column tiles x chunks, and a chunk is a whole number of segments (the
+    # -1 run is one), so no running value crosses workgroups
+    chunk_t = None
+    col_blocks = builtins.max(1, m // 1024)
+    desired = int(builtins.min(64, builtins.max(1, -(-2048 // col_blocks))))
+    if desired > 1 and n_t > 1 and not torch.cuda.is_current_stream_capturing():
+        sc = codes_sorted.cpu().numpy()
+        seg = np.flatnonzero(np.diff(sc)) + 1
+        target = builtins.max(1, -(-n_t // desired))
+        bounds = [0]
+        for b in seg:
+            if b - bounds[-1] >= target:
+                bounds.append(int(b))
+        bounds.append(int(n_t))
+        if len(bounds) > 2:
+            chunk_t = torch.tensor(bounds, dtype=torch.int64, device=dev)
+            c.chunk_offsets = chunk_t.data_ptr()
+            c.nchunks = len(bounds) - 1
+    c.stream = torch.cuda.current_stream(dev).cuda_stream
+    _ffi.check(lib.fh_grouped_scan_cols(
+        ctypes.byref(c), _SCAN_COLS_OPS[func], out.stride(0) if n_t > 1 else m))
+    for t in (values2d, codes_sorted, perm, chunk_t, out):
+        _record(t, torch.cuda.current_stream(dev))
+    return out
+
+
 def var_partials(
     group_idx, array, *, skipnan, size, labels2=None, grp_shape=None,
     global_counts=None, global_sums=None,

@@ -203,6 +203,182 @@ int run_scan(fh_call* c, V* out) {
   return 0;
 }
 
+/* ---- column form: grouped scans over the leading axis --------------------
+ * The walk of floxhip.hip's column kernels (rows in group order through the
+ * stable sort's perm, code/perm tiles staged in LDS, lanes along columns, VC
+ * columns per thread) with a store per element instead of a flush per group:
+ * each thread keeps ONE running value per column in a register, restarts it
+ * where the code changes, and writes it to out[perm[i] * ldo + c]. Every run
+ * of equal codes is a segment, the -1 run included (the reference's
+ * NaN-sentinel group, factorize.py:201-210). cur_g and acc live across the
+ * staging tiles, so a segment may span any number of them. A workgroup owns
+ * (column tile, chunk); a chunk is a whole number of segments, so no carry
+ * crosses workgroups. bfill is ffill with the chunk walked from its last row
+ * to its first. SCOLS_ROWS rows are loaded before the first of them is
+ * consumed (values and out never alias), which keeps that many independent
+ * loads in flight per thread. Addresses are row * ldm + c0 and row * ldo + c0
+ * in 64 bits. */
+constexpr int SCOLS_BLOCK = 256;
+constexpr int SCOLS_TTILE = 2048; /* rows per staged tile, as COLS_TTILE */
+#ifndef FH_SCOLS_ROWS
+#define FH_SCOLS_ROWS 4
+#endif
+constexpr int SCOLS_ROWS = FH_SCOLS_ROWS;
+/* columns per thread by value size: one 16-B vector, k_order_cols' caps */
+#ifndef FH_SCOLS_VC4B
+#define FH_SCOLS_VC4B 4
+#endif
+#ifndef FH_SCOLS_VC8B
+#define FH_SCOLS_VC8B 2
+#endif
+template <typename V>
+constexpr int SCOLS_VC = sizeof(V) == 4 ? FH_SCOLS_VC4B : FH_SCOLS_VC8B;
+
+template <typename V, int N>
+struct alignas(sizeof(V) * N) ScanVec {
+  V v[N];
+};
+
+/* one row of one column: `first` marks a segment's first row in walk order.
+ * The first row initialises the sums, so -0.0 survives as in np.cumsum;
+ * int64 wraps (added as unsigned). */
+template <typename V, int OP>
+__device__ __forceinline__ V scan_step(V acc, V v, bool first) {
+  if (OP == SCAN_FFILL || OP == SCAN_BFILL) return (first || !snan(v)) ? v : acc;
+  const V x = (OP == SCAN_NANCUMSUM && snan(v)) ? (V)0 : v;
+  if (first) return x;
+  if (std::is_same<V, int64_t>::value) return (V)((uint64_t)acc + (uint64_t)x);
+  return acc + x;
+}
+
+template <typename V, int OP, int VC>
+__launch_bounds__(SCOLS_BLOCK) __global__ void k_scan_cols(
+    const V* __restrict__ values, const int* __restrict__ codes_sorted,
+    const int* __restrict__ perm, int64_t n_t, int64_t m, int64_t ldm, int64_t ldo,
+    const int64_t* __restrict__ chunk_offs, V* __restrict__ out) {
+  constexpr bool REV = OP == SCAN_BFILL;
+  __shared__ int s_code[SCOLS_TTILE];
+  __shared__ int s_perm[SCOLS_TTILE];
+
+  const int64_t c0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * VC;
+  const bool col_act = c0 < m;
+  const bool full = c0 + VC <= m;
+  int64_t t_begin = 0, t_end = n_t;
+  if (chunk_offs) {
+    t_begin = chunk_offs[blockIdx.y];
+    t_end = chunk_offs[blockIdx.y + 1];
+  }
+
+  V acc[VC];
+#pragma unroll
+  for (int k = 0; k < VC; ++k) acc[k] = (V)0;
+  int cur_g = INT32_MIN; /* no code: codes are >= -1 */
+
+  const int64_t ntiles = (t_end - t_begin + SCOLS_TTILE - 1) / SCOLS_TTILE;
+  for (int64_t tt = 0; tt < ntiles; ++tt) {
+    const int64_t t0 = t_begin + (REV ? ntiles - 1 - tt : tt) * SCOLS_TTILE;
+    const int nt = (int)((t_end - t0 < SCOLS_TTILE) ? (t_end - t0) : SCOLS_TTILE);
+    __syncthreads();
+    for (int i = threadIdx.x; i < nt; i += blockDim.x) {
+      s_code[i] = codes_sorted[t0 + i];
+      s_perm[i] = perm[t0 + i];
+    }
+    __syncthreads();
+    if (!col_act) continue; /* block-uniform trip count: the barriers still meet */
+    for (int i0 = 0; i0 < nt; i0 += SCOLS_ROWS) {
+      ScanVec<V, VC> x[SCOLS_ROWS];
+      int g[SCOLS_ROWS];
+      int64_t row[SCOLS_ROWS];
+#pragma unroll
+      for (int u = 0; u < SCOLS_ROWS; ++u) {
+        if (i0 + u >= nt) break;
+        const int i = REV ? nt - 1 - (i0 + u) : i0 + u;
+        g[u] = s_code[i];
+        row[u] = (int64_t)s_perm[i];
+        const V* src = values + row[u] * ldm + c0;
+        if (VC > 1 && full) {
+          x[u] = *reinterpret_cast<const ScanVec<V, VC>*>(src);
+        } else {
+#pragma unroll
+          for (int k = 0; k < VC; ++k)
+            if (c0 + k < m) x[u].v[k] = src[k];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < SCOLS_ROWS; ++u) {
+        if (i0 + u >= nt) break;
+        const bool first = g[u] != cur_g;
+        cur_g = g[u];
+        ScanVec<V, VC> y;
+#pragma unroll
+        for (int k = 0; k < VC; ++k) {
+          acc[k] = scan_step<V, OP>(acc[k], x[u].v[k], first);
+          y.v[k] = acc[k];
+        }
+        V* dst = out + row[u] * ldo + c0;
+        if (VC > 1 && full) {
+          *reinterpret_cast<ScanVec<V, VC>*>(dst) = y;
+        } else {
+#pragma unroll
+          for (int k = 0; k < VC; ++k)
+            if (c0 + k < m) dst[k] = y.v[k];
+        }
+      }
+    }
+  }
+}
+
+/* launcher of k_scan_cols: the vector form needs both row strides a multiple
+ * of VC and both bases 16-B aligned (cols_plan's rule, applied to the output
+ * too), else one column per thread. Narrow arrays take smaller workgroups:
+ * the grid is column tiles x chunks, and fewer lanes per tile make more of
+ * them. */
+template <typename V, int OP>
+int launch_scan_cols(fh_call* c, int64_t ldo) {
+  hipStream_t stream = (hipStream_t)c->stream;
+  int vc = SCOLS_VC<V>;
+  if (c->ldm % vc != 0 || ldo % vc != 0 || ((uintptr_t)c->values % 16) != 0 ||
+      ((uintptr_t)c->out_sum % 16) != 0)
+    vc = 1;
+  const bool chunks = c->chunk_offsets != nullptr && c->nchunks > 0;
+  const int64_t nch = chunks ? c->nchunks : 1;
+  const int64_t lanes = (c->m + vc - 1) / vc;
+  int block = SCOLS_BLOCK;
+  while (block > 64 && ((lanes + block - 1) / block) * nch < 1024) block >>= 1;
+  const int64_t ncolblk = (lanes + block - 1) / block;
+  if (ncolblk > INT32_MAX) return 23;
+  dim3 grid((uint32_t)ncolblk, (uint32_t)nch);
+  const int64_t* offs = chunks ? (const int64_t*)c->chunk_offsets : nullptr;
+  auto launch = [&](auto vcc) -> int {
+    hipLaunchKernelGGL((k_scan_cols<V, OP, decltype(vcc)::value>), grid, dim3(block), 0,
+                       stream, (const V*)c->values, (const int*)c->labels,
+                       (const int*)c->perm, c->n, c->m, c->ldm, ldo, offs,
+                       (V*)c->out_sum);
+    FHS_CHECK(hipGetLastError());
+    return 0;
+  };
+  const int rc = vc > 1 ? launch(std::integral_constant<int, SCOLS_VC<V>>{})
+                        : launch(std::integral_constant<int, 1>{});
+  if (rc) return rc;
+  c->path_used = 3;
+  return 0;
+}
+
+/* sums for f32/f64/i64, fills for f32/f64 */
+template <typename V>
+int dispatch_scan_cols(fh_call* c, int op, int64_t ldo) {
+  switch (op) {
+    case SCAN_CUMSUM: return launch_scan_cols<V, SCAN_CUMSUM>(c, ldo);
+    case SCAN_NANCUMSUM: return launch_scan_cols<V, SCAN_NANCUMSUM>(c, ldo);
+    default: break;
+  }
+  if constexpr (!std::is_same<V, int64_t>::value) {
+    if (op == SCAN_FFILL) return launch_scan_cols<V, SCAN_FFILL>(c, ldo);
+    if (op == SCAN_BFILL) return launch_scan_cols<V, SCAN_BFILL>(c, ldo);
+  }
+  return 24;
+}
+
 template <typename V, typename L>
 int dispatch_scan_op(fh_call* c, int op, V* out) {
   switch (op) {
@@ -258,6 +434,30 @@ int fh_grouped_scan(fh_call* c, int op) {
                                    : dispatch_scan_op<int32_t, int32_t>(c, op, (int32_t*)c->out_sum);
     default:
       return 9;
+  }
+}
+
+/* grouped scan over the leading axis of an (n x m) array, in place on the
+ * caller's strided view (include/floxhip.h has the contract). No scratch, no
+ * host sync; every refusal returns before any launch. */
+int fh_grouped_scan_cols(fh_call* c, int op, int64_t ldo) {
+  if (!c || !c->values || !c->labels || !c->perm || !c->out_sum) return 22;
+  /* a single row has no stride to speak of; chunks ride gridDim.y */
+  if (c->n < 0 || c->m < 0 || c->n > INT32_MAX ||
+      (c->n > 1 && (c->ldm < c->m || ldo < c->m)) || c->nchunks < 0 ||
+      (c->chunk_offsets && c->nchunks > 65535))
+    return 23;
+  if (op < SCAN_CUMSUM || op > SCAN_BFILL) return 24;
+  if (c->vdtype != FH_F32 && c->vdtype != FH_F64 && c->vdtype != FH_I64) return 24;
+  if (c->vdtype == FH_I64 && op >= SCAN_FFILL) return 24;
+  if (c->n == 0 || c->m == 0) {
+    c->path_used = 3;
+    return 0;
+  }
+  switch (c->vdtype) {
+    case FH_F32: return dispatch_scan_cols<float>(c, op, ldo);
+    case FH_F64: return dispatch_scan_cols<double>(c, op, ldo);
+    default: return dispatch_scan_cols<int64_t>(c, op, ldo);
   }
 }
 

@@ -40,6 +40,22 @@ Supported options:
       at any size, where the call is eligible: the conditions of
       cols_order_funcs, no hipGraph capture, and no group longer than the
       kernel's capacity (2048 rows) (core.py).
+  cols_scan: False sends cumsum/nancumsum/ffill/bfill over leading dims
+      through the lead fold (a flattened copy, composite int64 labels and a
+      device-wide radix sort of N * lead_M pairs with about 70 B of scratch
+      per element, limited to N * lead_M < 2**32); on (the default) the
+      column kernel walks each group's rows with one running value per
+      column, reading the caller's strided view in place and writing the
+      result once, at any size, where the call is eligible: the (N, lead_M)
+      view has unit column stride without a copy (time-major storage read
+      through a permute view), f32/f64/i64 values after promotion for the
+      sums and f32/f64 for the fills, not distributed, no datetime values,
+      at least one row, N < 2**31, no hipGraph capture, and lead_M >=
+      cols_scan_min_cols (scan.py).
+  cols_scan_min_cols: the narrowest lead_M that takes the column form. Its
+      parallelism is column tiles times group-aligned row chunks, so a
+      narrow array with few long groups is left to the fold; None = the
+      measured default (profiles/r10_cols_scan.md).
 """
 
 from __future__ import annotations
@@ -58,6 +74,8 @@ OPTIONS = {
     "fused_many": None,               # None = on
     "cols_order_funcs": None,         # None = on
     "cols_sorted_funcs": None,        # None = on
+    "cols_scan": None,                # None = on
+    "cols_scan_min_cols": None,       # None = the measured default
 }
 
 _CACHE_FIELDS = {
@@ -68,7 +86,7 @@ _CACHE_FIELDS = {
 
 
 def _apply(name, value):
-    from . import core, distributed, label_cache
+    from . import core, distributed, label_cache, scan
 
     if name in _CACHE_FIELDS:
         field = _CACHE_FIELDS[name]
@@ -106,6 +124,16 @@ def _apply(name, value):
         if value is not None:
             core.COLS_SORTED_FUNCS = bool(value)
         return ("cols_sorted_funcs", old)
+    if name == "cols_scan":
+        old = scan.COLS_SCAN
+        if value is not None:
+            scan.COLS_SCAN = bool(value)
+        return ("cols_scan", old)
+    if name == "cols_scan_min_cols":
+        old = scan.COLS_SCAN_MIN_COLS
+        if value is not None:
+            scan.COLS_SCAN_MIN_COLS = int(value)
+        return ("cols_scan_min_cols", old)
     if name == "sparse_combine_ngroups":
         old = distributed.SPARSE_NGROUPS
         if value is not None:
@@ -122,7 +150,7 @@ def _apply(name, value):
 
 
 def _restore(name, old):
-    from . import core, distributed, label_cache
+    from . import core, distributed, label_cache, scan
 
     if name in _CACHE_FIELDS:
         label_cache.CACHE.configure(**{_CACHE_FIELDS[name]: old})
@@ -138,6 +166,10 @@ def _restore(name, old):
         core.COLS_ORDER_FUNCS = old
     elif name == "cols_sorted_funcs":
         core.COLS_SORTED_FUNCS = old
+    elif name == "cols_scan":
+        scan.COLS_SCAN = old
+    elif name == "cols_scan_min_cols":
+        scan.COLS_SCAN_MIN_COLS = old
     elif name == "sparse_combine_ngroups":
         distributed.SPARSE_NGROUPS = old
     elif name == "sparse_combine_fraction":

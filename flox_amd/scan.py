@@ -168,18 +168,19 @@ def groupby_scan(
             raise NotImplementedError("scan over an axis subset: next row")
 
     orig_shape = arr.shape
-    vals = arr.reshape(-1)
-    if vals.numel() == 0:
-        out0 = torch.empty_like(vals).reshape(orig_shape)
+    if arr.numel() == 0:
+        out0 = torch.empty_like(arr.reshape(-1)).reshape(orig_shape)
         if return_numpy:
             o = out0.cpu().numpy()
             return o.astype(dt_dtype) if dt_dtype is not None else o
         return out0
-    # integer promotion like np.cumsum (sub-platform ints accumulate in intp)
-    if func in ("cumsum", "nancumsum") and vals.dtype in (torch.int32, torch.bool):
-        vals = vals.to(torch.int64)
-    if vals.dtype == torch.bool:
-        vals = vals.to(torch.int64)
+    # integer promotion like np.cumsum (sub-platform ints accumulate in intp);
+    # done on the array as laid out (.to keeps a permute view's strides), the
+    # flattening is left to whichever path runs
+    if func in ("cumsum", "nancumsum") and arr.dtype in (torch.int32, torch.bool):
+        arr = arr.to(torch.int64)
+    if arr.dtype == torch.bool:
+        arr = arr.to(torch.int64)
 
     if expected_groups is not None and not isinstance(expected_groups, tuple):
         expected_groups = (expected_groups,)
@@ -198,6 +199,104 @@ def groupby_scan(
         ngroups *= f.ngroups
     labels, labels2, grp_pair = _combined_codes(facs)
 
+    if distributed_combine is None:
+        distributed_combine = distributed.is_active()
+    out = None
+    if lead_M > 1:
+        vt = _cols_view(arr, len(by_shape), lead_M)
+        if _cols_scan_ok(func, vt, lead_M, dt_dtype,
+                         distributed_combine and distributed.is_active()):
+            # the column form: no flattened copy, no composite labels, no
+            # device-wide sort, no scratch, no limit on N * lead_M. The
+            # output takes the view's own strides, so reads and writes are
+            # both coalesced.
+            from .aggregate_hip import grouped_scan_cols
+            from .core import _bounded_codes
+
+            codes_full = _bounded_codes(labels, labels2, grp_pair, ngroups)
+            scodes64, perm64 = torch.sort(codes_full, stable=True)
+            out_full = torch.empty_like(arr)  # preserve_format: arr's strides
+            out_vt = _cols_view(out_full, len(by_shape), lead_M)
+            if out_vt is None:
+                out_full = None  # a sliced layout, which empty_like densified
+            res = grouped_scan_cols(
+                vt, scodes64.to(torch.int32), perm64.to(torch.int32), func, out=out_vt
+            )
+            out = out_full if out_full is not None else (
+                res.reshape(tuple(by_shape) + tuple(orig_shape[: arr.ndim - len(by_shape)]))
+                .movedim(tuple(range(len(by_shape))),
+                         tuple(range(arr.ndim - len(by_shape), arr.ndim)))
+            )
+    if out is None:
+        out = _scan_fold(arr, func, lead_M, labels, labels2, grp_pair, ngroups,
+                         distributed_combine, device).reshape(orig_shape)
+
+    if dtype is not None:
+        td = torch.from_numpy(np.empty(0, dtype=np.dtype(dtype))).dtype
+        out = out.to(td)
+    if return_numpy:
+        out_np = out.cpu().numpy()
+        if dt_dtype is not None:
+            out_np = out_np.astype(dt_dtype)  # int64 counts reinterpret
+        if small_dtype is not None and dtype is None:
+            out_np = _cast_back_small(out_np, func, small_dtype)
+        return out_np
+    return out
+
+
+# options.cols_scan: scans over leading dims take the column kernel
+# (fh_grouped_scan_cols) where the call is eligible (_cols_scan_ok) instead of
+# the lead fold
+COLS_SCAN = True
+# options.cols_scan_min_cols: the narrowest lead_M that takes it. The grid is
+# column tiles x group-aligned chunks, so a narrow array with few long groups
+# leaves most of the chip idle and the fold wins there. Measured at 2^26
+# elements (profiles/r10_cols_scan.md): with 24 groups the column form wins
+# from 1024 columns, with 2 groups it is still 3 % behind at 4096 and 3.3x
+# ahead at 16384, the smallest width of the sweep where it loses in neither.
+COLS_SCAN_MIN_COLS = 16384
+
+
+def _cols_view(arr, nbydims, lead_M):
+    """The (N, lead_M) view of arr with the grouped dims in front, as
+    core._select_engine builds it, or None where it has no unit column stride
+    without a copy."""
+    N = arr.numel() // lead_M
+    arr_t = arr.movedim(tuple(range(arr.ndim - nbydims, arr.ndim)), tuple(range(nbydims)))
+    try:
+        vt = arr_t.view((N, lead_M))
+    except RuntimeError:
+        return None
+    return vt if vt.stride(1) == 1 else None
+
+
+def _cols_scan_ok(func, vt, lead_M, dt_dtype, dist_on):
+    """Whether a scan over leading dims takes the column form; vt is
+    _cols_view's answer. Everything else keeps the lead fold with its results
+    and exceptions. The chunk plan reads the sorted codes on the host, which a
+    stream under capture cannot."""
+    return (
+        COLS_SCAN
+        and vt is not None
+        and lead_M >= COLS_SCAN_MIN_COLS
+        and vt.dtype in (
+            (torch.float32, torch.float64, torch.int64)
+            if func in ("cumsum", "nancumsum") else (torch.float32, torch.float64)
+        )
+        and not dist_on
+        and dt_dtype is None
+        and vt.shape[0] > 0
+        and vt.shape[0] < 2**31
+        and not torch.cuda.is_current_stream_capturing()
+        and _ffi.has_scan_cols()
+    )
+
+
+def _scan_fold(arr, func, lead_M, labels, labels2, grp_pair, ngroups,
+               distributed_combine, device):
+    """The 1-D scan (fh_grouped_scan) over the C-order flattened array, leading
+    dims folded into the group codes. Returns the flat result."""
+    vals = arr.reshape(-1)
     if lead_M > 1:
         # leading array dims: fold the lead index into the group codes
         # (lead*(ngroups+1) + code, +1 so every column keeps its own
@@ -246,8 +345,10 @@ def groupby_scan(
     c.stream = torch.cuda.current_stream(device).cuda_stream
     # sorted-labels fast path (the reference's issorted check,
     # aggregate_flox.py:9-23): nondecreasing in-range codes skip the
-    # device radix sort entirely — the common time-ordered layout
-    if labels.numel() > 1:
+    # device radix sort entirely — the common time-ordered layout. The probe
+    # reads back to the host, which a stream under capture cannot: there the
+    # radix sort runs (stable, so the result is the same)
+    if labels.numel() > 1 and not torch.cuda.is_current_stream_capturing():
         in_range = bool(
             ((labels >= 0) & (labels < ngroups)).all().item()
         ) if labels2 is None else False
@@ -259,8 +360,6 @@ def groupby_scan(
     for t in (vals, labels, labels2, scratch, out):
         _record(t, torch.cuda.current_stream(device))
 
-    if distributed_combine is None:
-        distributed_combine = distributed.is_active()
     if distributed_combine and distributed.is_active():
         if labels2 is not None:
             codes = labels.to(torch.int64) * grp_pair[1] + labels2.to(torch.int64)
@@ -278,16 +377,4 @@ def groupby_scan(
             (codes >= 0) & (codes < ngroups), codes, torch.full_like(codes, ngroups)
         )
         out = distributed.scan_carry_exchange(out, vals, codes, ngroups + 1, func)
-
-    if dtype is not None:
-        td = torch.from_numpy(np.empty(0, dtype=np.dtype(dtype))).dtype
-        out = out.to(td)
-    out = out.reshape(orig_shape)
-    if return_numpy:
-        out_np = out.cpu().numpy()
-        if dt_dtype is not None:
-            out_np = out_np.astype(dt_dtype)  # int64 counts reinterpret
-        if small_dtype is not None and dtype is None:
-            out_np = _cast_back_small(out_np, func, small_dtype)
-        return out_np
     return out

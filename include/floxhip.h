@@ -298,6 +298,36 @@ int fh_grouped_quantile_cols(fh_call* c, int nq, int64_t max_seg_rows);
  * dtype (2048 for all four); 0 for an unknown dtype */
 int64_t fh_quantile_cols_max_rows(int vdtype);
 
+/* grouped scans over the leading axis of a multi-column array: the column
+ * form of fh_grouped_scan, op as there (0 cumsum, 1 nancumsum, 2 ffill,
+ * 3 bfill). Inputs as fh_grouped_reduce_cols: values n x m with row stride
+ * ldm and unit column stride, labels = int32 codes in [-1, ngroups) sorted
+ * ascending, perm = the int32 permutation of a STABLE sort of the codes. A
+ * scan depends on the row order inside a group, so, unlike the arg sets,
+ * "any perm that sorts the codes" is NOT enough: equal codes must keep their
+ * original row order. chunk_offsets / nchunks (optional) are group-aligned
+ * row chunks as there: one workgroup walks (column tile, chunk), and a chunk
+ * must be a whole number of runs of equal codes; nchunks <= 65535. Without
+ * them one workgroup per column tile walks all rows. Every run of equal codes
+ * is a segment and scans as one group, the -1 run included (the reference's
+ * NaN-sentinel group). out_sum receives value-dtype n x m with row stride
+ * ldo: element (perm[i], c) goes to out_sum[perm[i] * ldo + c]; out_sum must
+ * not overlap values. cumsum adds sequentially in the value dtype in row
+ * order, the segment's first row initialising the sum (-0.0 survives, a NaN
+ * poisons the rest of its segment, int64 wraps); nancumsum the same with NaN
+ * contributing 0; ffill carries the last non-NaN value and leaves NaN before
+ * the first; bfill is ffill walked from the segment's last row. Served:
+ * sums for FH_F32 / FH_F64 / FH_I64, fills for FH_F32 / FH_F64. The values
+ * are read once and written once, in place, with no scratch, no host sync and
+ * no limit on n * m (offsets are 64-bit; n itself fits int32). ngroups is
+ * not read. path_used = 3. Errors (no launch, outputs untouched): 22 = a
+ * missing buffer (values, labels, perm, out_sum); 23 = a negative extent, n
+ * beyond int32, a row stride below m, or nchunks out of range; 24 = an
+ * unknown op or a (dtype, op) pair that is not served. fh_error_string
+ * predates these codes. Came without a new revision (fh_call is unchanged): a
+ * caller detects it by the symbol. */
+int fh_grouped_scan_cols(fh_call* c, int op, int64_t ldo);
+
 /* pack (order-preserving 32-bit value encoding, global row index) into one
  * int64 key per row, so that a grouped MIN over the keys is argmin/argmax
  * with np.argmin's first-occurrence tie-break (the packed form of the
@@ -327,7 +357,8 @@ int fh_version(void);
  * needs a library with fh_abi_revision() >= R. The column forms of
  * FH_SET_IDXMIN/IDXMAX, FH_SET_ARGMIN_COLS/ARGMAX_COLS and fh_cols_supports
  * came without a new revision (it stays 6: fh_call is unchanged): a caller
- * detects them by the fh_cols_supports symbol and its answer. */
+ * detects them by the fh_cols_supports symbol and its answer. Likewise
+ * fh_grouped_quantile_cols and fh_grouped_scan_cols, each by its own symbol. */
 int fh_abi_revision(void);
 
 #ifdef __cplusplus
