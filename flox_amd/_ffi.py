@@ -169,8 +169,19 @@ def load_library():
             ctypes.POINTER(FhCall), ctypes.c_int, ctypes.c_int64,
         ]
         lib.fh_grouped_scan_cols.restype = ctypes.c_int
+    # and the radix-select column form of the quantile family
+    if hasattr(lib, "fh_grouped_quantile_select_cols"):
+        lib.fh_grouped_quantile_select_cols.argtypes = [
+            ctypes.POINTER(FhCall), ctypes.c_int,
+        ]
+        lib.fh_grouped_quantile_select_cols.restype = ctypes.c_int
     _lib = lib
     return lib
+
+
+def has_select_cols() -> bool:
+    """Whether the loaded library has fh_grouped_quantile_select_cols."""
+    return hasattr(load_library(), "fh_grouped_quantile_select_cols")
 
 
 def has_scan_cols() -> bool:
@@ -214,7 +225,14 @@ _QCOLS_ERRORS = {
 }
 
 
-def check(code: int) -> None:
+# fh_grouped_quantile_select_cols gives code 22 its own meaning
+_SELECT_COLS_ERRORS = {
+    22: "fh_grouped_quantile_select_cols: missing values/labels/perm/out_sum/q "
+        "buffer, nq below 1, or an extent that is negative or beyond int32 rows",
+}
+
+
+def check(code: int, errors=_QCOLS_ERRORS) -> None:
     if code != 0:
-        msg = _QCOLS_ERRORS.get(code) or load_library().fh_error_string(code).decode()
+        msg = errors.get(code) or load_library().fh_error_string(code).decode()
         raise RuntimeError(f"floxhip error {code}: {msg}")

@@ -738,10 +738,12 @@ def grouped_mode(
 
 
 def _sorted_cols(values2d, codes_sorted, perm, ngroups, q_t, *, skipnan, max_seg_rows, want_count):
-    # one fh_grouped_quantile_cols call: q_t None = mode
+    # one fh_grouped_quantile_cols call: q_t None = mode. max_seg_rows None:
+    # fh_grouped_quantile_select_cols, which takes groups of any length
     lib = _ffi.load_library()
-    if not hasattr(lib, "fh_grouped_quantile_cols"):
-        raise RuntimeError("libfloxhip.so lacks fh_grouped_quantile_cols: rebuild the extension")
+    entry = "fh_grouped_quantile_cols" if max_seg_rows is not None else "fh_grouped_quantile_select_cols"
+    if not hasattr(lib, entry):
+        raise RuntimeError(f"libfloxhip.so lacks {entry}: rebuild the extension")
     _require_gpu_tensor(values2d, "values")
     assert values2d.ndim == 2 and values2d.stride(1) == 1
     assert codes_sorted.dtype == torch.int32 and perm.dtype == torch.int32
@@ -774,7 +776,11 @@ def _sorted_cols(values2d, codes_sorted, perm, ngroups, q_t, *, skipnan, max_seg
         count = torch.empty((ngroups, m), dtype=torch.int64, device=dev)
         c.out_count = count.data_ptr()
     c.stream = torch.cuda.current_stream(dev).cuda_stream
-    _ffi.check(lib.fh_grouped_quantile_cols(ctypes.byref(c), nq, int(max_seg_rows)))
+    if max_seg_rows is not None:
+        _ffi.check(lib.fh_grouped_quantile_cols(ctypes.byref(c), nq, int(max_seg_rows)))
+    else:
+        _ffi.check(lib.fh_grouped_quantile_select_cols(ctypes.byref(c), nq),
+                   _ffi._SELECT_COLS_ERRORS)
     for t in (values2d, codes_sorted, perm, q_t, out, count):
         _record(t, torch.cuda.current_stream(dev))
     return (out, count) if want_count else out
@@ -803,6 +809,28 @@ def grouped_quantile_cols(
     ).contiguous()
     return _sorted_cols(values2d, codes_sorted, perm, ngroups, q_t, skipnan=skipnan,
                         max_seg_rows=max_seg_rows, want_count=want_count)
+
+
+def grouped_quantile_select_cols(
+    values2d: torch.Tensor,
+    codes_sorted: torch.Tensor,
+    perm: torch.Tensor,
+    ngroups: int,
+    q,
+    *,
+    skipnan: bool = False,
+    want_count: bool = False,
+):
+    """grouped_quantile_cols for groups of any length: each (group, column)'s
+    order statistics found by radix selection over the segment
+    (fh_grouped_quantile_select_cols), several reads of the values instead of
+    one and no bound on a group's row count. Same tensors, same returns, the
+    same bits."""
+    q_t = torch.as_tensor(
+        np.atleast_1d(np.asarray(q, dtype=np.float64)), device=values2d.device
+    ).contiguous()
+    return _sorted_cols(values2d, codes_sorted, perm, ngroups, q_t, skipnan=skipnan,
+                        max_seg_rows=None, want_count=want_count)
 
 
 def grouped_mode_cols(

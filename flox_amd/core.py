@@ -68,6 +68,20 @@ _COLS_ORDER = _ARG_FUNCS + _FIRST_LAST_FUNCS
 # eligible (_cols_sorted_ok) instead of the lead fold
 COLS_SORTED_FUNCS = True
 _COLS_SORTED = _QUANTILE_FUNCS + ("mode", "nanmode")
+# options.cols_select_funcs: where a group is longer than the sort-in-LDS
+# capacity, the quantile family takes the radix-select column kernel
+# (fh_grouped_quantile_select_cols) instead of the lead fold. It extends the
+# sorted form: cols_sorted_funcs=False turns both off.
+COLS_SELECT_FUNCS = True
+_COLS_SELECT = _QUANTILE_FUNCS
+# options.cols_select_min_cols: the narrowest lead_M that takes it. The grid
+# is column tiles x groups, so a narrow array with few long groups leaves
+# most of the chip idle and the fold wins. Measured on MI355X at 2**26
+# elements, nanmedian, 1 and 4 groups (profiles/r11_cols_select.md): f32 wins
+# from 8192 columns with one group (3.35 vs 4.39 ms) and from 2048 with four;
+# f64 loses at 8192 with one group (9.05 vs 7.97 ms) and wins from 16384
+# (4.67 vs 8.07 ms). Never below one column tile of the kernel's plan (64).
+COLS_SELECT_MIN_COLS = 16384
 
 _TORCH_TO_NP = {
     torch.float32: np.dtype("float32"),
@@ -810,6 +824,7 @@ class _Plan:
         # _select_engine, _fold_lead
         "label_src", "row_offset", "cols", "many_served", "lead_folded",
         "arg_localize_N", "base_ngroups", "cols_order", "cols_sorted_rows",
+        "cols_select",
     )
 
 
@@ -1008,7 +1023,9 @@ def _cols_sorted_ok(p, vt):
     count) when it does. Where a condition fails the call keeps the lead fold
     with its results and exceptions. The largest group is read from the
     sorted codes on the host, the copy grouped_partials_cols also makes for
-    its chunk plan: a stream under capture cannot, and keeps the fold."""
+    its chunk plan: a stream under capture cannot, and keeps the fold. A group
+    over the capacity sends the quantile family to the radix-select kernel
+    (p.cols_select) where that is on, present and the array wide enough."""
     if not (
         COLS_SORTED_FUNCS
         and p.func in _COLS_SORTED
@@ -1028,7 +1045,14 @@ def _cols_sorted_ok(p, vt):
     edges = np.flatnonzero(np.diff(sc)) + 1
     longest = int(np.diff(np.concatenate(([0], edges, [sc.size]))).max()) if sc.size else 1
     if longest > cap:
-        return False
+        if not (
+            COLS_SELECT_FUNCS
+            and p.func in _COLS_SELECT
+            and p.lead_M >= COLS_SELECT_MIN_COLS
+            and _ffi.has_select_cols()
+        ):
+            return False
+        p.cols_select = True
     p.cols_sorted_rows = longest
     return True
 
@@ -1039,7 +1063,7 @@ def _select_engine(p, by):
     the lead fold (_fold_lead) also rewrites its vals, labels and ngroups."""
     p.label_src, p.row_offset, p.cols = None, p.shard_row_offset, None
     p.many_served = p.lead_folded = p.cols_order = False
-    p.cols_sorted_rows = None
+    p.cols_sorted_rows, p.cols_select = None, False
     many, facs = p.many, p.facs
     if p.lead_M == 1:
         # label-code cache key: the CALLER's by object(s) — `labels` is a
@@ -1099,8 +1123,9 @@ def _select_engine(p, by):
         p.cols_order = True
         return _EngineCols(p)
     if _cols_sorted_ok(p, vt):
-        # each group's rows sorted in LDS: no composite labels, no flattened
-        # copy, no device-wide sort, no limit on N * lead_M. Inside
+        # each group's rows sorted in LDS, or its order statistics selected
+        # by radix passes where it is too long for that: no composite labels,
+        # no flattened copy, no device-wide sort, no limit on N * lead_M. Inside
         # groupby_reduce_many these names share the factorization only.
         return _EngineCols(p)
     # (the column view and the sort above go unused here: kept, since
@@ -1147,16 +1172,22 @@ def _quantile_finish(p, resq, scalar_q, nq, counts):
 def _family_quantile_cols(p, eng):
     """Quantiles over leading dims, sorted in LDS: (nq, ngroups, M) from one
     read of the (N, lead_M) view; the kernel's non-NaN counts stand in for
-    the SET_COUNT pass of the min_count rule."""
-    from .aggregate_hip import grouped_quantile_cols
+    the SET_COUNT pass of the min_count rule. With a group too long to sort
+    in LDS (p.cols_select) the radix-select kernel gives the same."""
+    from .aggregate_hip import grouped_quantile_cols, grouped_quantile_select_cols
 
     q_arr, scalar_q = _quantile_q(p)
     vt, scodes, perm = p.cols
     want = p.min_count_ > 0
-    r = grouped_quantile_cols(
-        vt, scodes, perm, p.ngroups, q_arr, skipnan=p.agg.skipnan,
-        max_seg_rows=p.cols_sorted_rows, want_count=want,
-    )
+    if p.cols_select:
+        r = grouped_quantile_select_cols(
+            vt, scodes, perm, p.ngroups, q_arr, skipnan=p.agg.skipnan, want_count=want,
+        )
+    else:
+        r = grouped_quantile_cols(
+            vt, scodes, perm, p.ngroups, q_arr, skipnan=p.agg.skipnan,
+            max_seg_rows=p.cols_sorted_rows, want_count=want,
+        )
     resq, counts = r if want else (r, None)
     return _quantile_finish(p, resq, scalar_q, len(q_arr), lambda: counts)
 

@@ -22,6 +22,7 @@
 
 #include "../../include/floxhip.h"
 #include "../../include/floxhip_qcols.h"
+#include "../../include/floxhip_selcols.h"
 
 #define FHQ_CHECK(x)                                \
   do {                                              \
@@ -175,6 +176,22 @@ __device__ __forceinline__ int64_t sorted_nonnan(KeyAt key_at, int64_t full) {
 /* numpy method="linear" quantile; reference _lerp (aggregate_flox.py:26-47)
  * including the t>=0.5 form. NaN for an empty group, an all-NaN group, and a
  * NaN-containing group without skipna. actual = sorted_nonnan(key_at, full). */
+/* the two positions quantile_of_sorted reads for `actual` > 0 non-NaN rows;
+ * returns the virtual index q * (actual - 1) */
+__device__ __forceinline__ double quantile_ranks(int64_t actual, double q, int64_t& lo_i,
+                                                 int64_t& hi_i) {
+  const double vi = q * (double)(actual - 1);
+  lo_i = (int64_t)floor(vi);
+  hi_i = (int64_t)ceil(vi);
+  /* q in [0, 1] needs only the first and the last clamp; the other two
+   * keep a q outside it inside the run */
+  if (lo_i < 0) lo_i = 0;
+  if (lo_i > actual - 1) lo_i = actual - 1;
+  if (hi_i < 0) hi_i = 0;
+  if (hi_i > actual - 1) hi_i = actual - 1;
+  return vi;
+}
+
 template <typename V, typename KeyAt>
 __device__ __forceinline__ double quantile_of_sorted(KeyAt key_at, int64_t full,
                                                      int64_t actual, double q, int skipna) {
@@ -182,14 +199,8 @@ __device__ __forceinline__ double quantile_of_sorted(KeyAt key_at, int64_t full,
   if (full > 0) {
     const bool nanmask = actual != full;
     if (actual > 0 && (skipna || !nanmask)) {
-      const double vi = q * (double)(actual - 1);
-      int64_t lo_i = (int64_t)floor(vi), hi_i = (int64_t)ceil(vi);
-      /* q in [0, 1] needs only the first and the last clamp; the other two
-       * keep a q outside it inside the run */
-      if (lo_i < 0) lo_i = 0;
-      if (lo_i > actual - 1) lo_i = actual - 1;
-      if (hi_i < 0) hi_i = 0;
-      if (hi_i > actual - 1) hi_i = actual - 1;
+      int64_t lo_i, hi_i;
+      const double vi = quantile_ranks(actual, q, lo_i, hi_i);
       const double a = (double)dec_key<V>(key_at(lo_i));
       const double b = (double)dec_key<V>(key_at(hi_i));
       const double tq = vi - (double)lo_i;
@@ -405,6 +416,233 @@ int run_quantile_cols(fh_call* c, int nq, int64_t max_seg_rows) {
                  : launch_sortsel_cols<V, false>(c, nq, pl);
 }
 
+/* ---- column form for groups of any length: radix selection ---------------
+ * Grid, segment search and row addressing as k_sortsel_cols (lanes along
+ * columns, the workgroup's other threads stride the rows), but no row is
+ * kept: every pass reads the segment again and counts one DB-bit digit of the
+ * keys, most significant first, into LDS histograms [slot][bin][column]
+ * (column fastest: the lanes of a wave hit distinct addresses). A slot is one
+ * q: its key prefix so far and the rank that remains inside that prefix.
+ * After a pass one thread per (slot, column) walks the slot's bins and
+ * appends the bin its rank falls in. Pass 0 has the same (empty) prefix in
+ * every slot, so one histogram serves them all; it also counts the canonical
+ * NaN keys per column, so `actual` and with it the ranks floor(vi) / ceil(vi)
+ * (quantile_ranks) are known before the first bin is chosen. The passes give
+ * the key at floor(vi). Where some (slot, column) has ceil(vi) != floor(vi),
+ * one more read counts the keys <= that key and finds the smallest key above
+ * it: the key at floor(vi) + 1 is the same key when the count reaches
+ * floor(vi) + 2, else that successor. quantile_of_sorted then runs on the
+ * two keys. NaN keys are all ones, sort last and are never selected while a
+ * rank is below `actual`. Counters are 32-bit: len <= n < 2^31. */
+__device__ __forceinline__ void lds_min(uint32_t* p, uint32_t v) { atomicMin(p, v); }
+__device__ __forceinline__ void lds_min(uint64_t* p, uint64_t v) {
+  atomicMin(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
+}
+
+template <typename V>
+__global__ __launch_bounds__(1024) void k_radixsel_cols(
+    const V* __restrict__ values, const int32_t* __restrict__ codes,
+    const int32_t* __restrict__ perm, int64_t n, int64_t m, int64_t ldm,
+    int64_t ngroups, int64_t g_base, int64_t ntiles, int logC,
+    const double* __restrict__ q, int nq, int skipna, double* __restrict__ out,
+    int64_t* __restrict__ out_count) {
+  using K = qkey_t<V>;
+  constexpr int KB = (int)sizeof(K) * 8, DB = FH_SELCOLS_DIGIT_BITS, NB = 1 << DB;
+  constexpr int NPASS = KB / DB, MAXS = FH_SELCOLS_MAX_SLOTS;
+  constexpr K NAN_KEY = ~(K)0;
+  extern __shared__ __align__(16) unsigned char selcols_lds[];
+  const int C = 1 << logC;
+  const int nsc = nq << logC; /* (slot, column) pairs: <= blockDim.x */
+  uint32_t* hist = reinterpret_cast<uint32_t*>(selcols_lds); /* [nq][NB][C] */
+  K* pref = reinterpret_cast<K*>(hist + (size_t)nsc * NB);   /* [nq][C] */
+  K* succ = pref + nsc;                                       /* [nq][C] */
+  uint32_t* rank = reinterpret_cast<uint32_t*>(succ + nsc);  /* [nq][C] */
+  uint32_t* cle = rank + nsc;                                 /* [nq][C] */
+  uint32_t* nanc = cle + nsc;                                 /* [C] */
+  const int64_t g = g_base + (int64_t)blockIdx.x / ntiles;
+  const int64_t c0 = ((int64_t)blockIdx.x % ntiles) << logC;
+  if (g >= ngroups) return;
+  const int tid = threadIdx.x, nthr = blockDim.x;
+
+  /* segment [start, start + len) of code g; rows of code -1 sort first */
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((int64_t)codes[mid] < g)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  const int64_t start = lo;
+  hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((int64_t)codes[mid] <= g)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  const int len = (int)(lo - start); /* < 2^31 */
+
+  const int c = tid & (C - 1);
+  const int64_t col = c0 + c;
+  const bool col_ok = col < m;
+  const int r0 = tid >> logC, rstep = nthr >> logC;
+  /* this thread's (slot, column) where tid < nsc */
+  const int my_s = tid >> logC;
+  const bool owner = tid < nsc;
+  const double my_q = owner ? q[my_s] : 0.0;
+  int need = 0;
+
+  if (len > 0) {
+    if (owner) {
+      pref[tid] = 0;
+      succ[tid] = NAN_KEY;
+      cle[tid] = 0;
+    }
+    if (tid < C) nanc[tid] = 0;
+    for (int pass = 0; pass < NPASS; ++pass) {
+      const int shift = KB - DB * (pass + 1);
+      const int nh = (pass == 0 ? C : nsc) * NB;
+      for (int t = tid; t < nh; t += nthr) hist[t] = 0;
+      __syncthreads();
+      if (col_ok) {
+        if (pass == 0) {
+          uint32_t my_nan = 0;
+#pragma unroll 4
+          for (int r = r0; r < len; r += rstep) {
+            const K key = enc_key<V>(values[(int64_t)perm[start + r] * ldm + col]);
+            if (is_float_v<V>) my_nan += key == NAN_KEY;
+            atomicAdd(&hist[((int)(key >> shift) << logC) + c], 1u);
+          }
+          if (is_float_v<V> && my_nan) atomicAdd(&nanc[c], my_nan);
+        } else {
+          K top[MAXS];
+#pragma unroll
+          for (int s = 0; s < MAXS; ++s)
+            top[s] = s < nq ? (K)(pref[(s << logC) + c] >> (shift + DB)) : (K)0;
+#pragma unroll 4
+          for (int r = r0; r < len; r += rstep) {
+            const K key = enc_key<V>(values[(int64_t)perm[start + r] * ldm + col]);
+            const int d = (int)((key >> shift) & (K)(NB - 1));
+            const K ktop = key >> (shift + DB);
+#pragma unroll
+            for (int s = 0; s < MAXS; ++s)
+              if (s < nq && ktop == top[s]) atomicAdd(&hist[((s * NB + d) << logC) + c], 1u);
+          }
+        }
+      }
+      __syncthreads();
+      if (owner) {
+        uint32_t rem;
+        if (pass == 0) {
+          const int64_t actual = (int64_t)len - (int64_t)nanc[c];
+          int64_t lo_i = 0, hi_i = 0;
+          if (actual > 0) quantile_ranks(actual, my_q, lo_i, hi_i);
+          need = hi_i != lo_i;
+          rem = (uint32_t)lo_i;
+        } else {
+          rem = rank[tid];
+        }
+        const uint32_t* h = hist + (((pass == 0 ? 0 : my_s) * NB) << logC) + c;
+        uint32_t cum = 0, below = 0;
+        int bin = 0;
+#pragma unroll 8
+        for (int b = 0; b < NB; ++b) {
+          cum += h[b << logC];
+          if (cum <= rem) {
+            bin = b + 1;
+            below = cum;
+          }
+        }
+        /* a column past m has an empty histogram: keep the digit in range */
+        if (bin > NB - 1) bin = NB - 1;
+        pref[tid] |= (K)bin << shift;
+        rank[tid] = rem - below;
+      }
+      __syncthreads();
+    }
+    if (__syncthreads_or(need)) {
+      if (col_ok) {
+        K sel[MAXS], mn[MAXS];
+        uint32_t cn[MAXS];
+#pragma unroll
+        for (int s = 0; s < MAXS; ++s) {
+          sel[s] = s < nq ? pref[(s << logC) + c] : NAN_KEY;
+          mn[s] = NAN_KEY;
+          cn[s] = 0;
+        }
+#pragma unroll 4
+        for (int r = r0; r < len; r += rstep) {
+          const K key = enc_key<V>(values[(int64_t)perm[start + r] * ldm + col]);
+#pragma unroll
+          for (int s = 0; s < MAXS; ++s)
+            if (s < nq) {
+              cn[s] += key <= sel[s];
+              if (key > sel[s] && key < mn[s]) mn[s] = key;
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < MAXS; ++s)
+          if (s < nq) {
+            atomicAdd(&cle[(s << logC) + c], cn[s]);
+            lds_min(&succ[(s << logC) + c], mn[s]);
+          }
+      }
+      __syncthreads();
+    }
+  }
+
+  if (owner && col_ok) {
+    int64_t actual = 0, lo_i = 0, hi_i = 0;
+    K klo = NAN_KEY, khi = NAN_KEY;
+    if (len > 0) {
+      actual = (int64_t)len - (int64_t)nanc[c];
+      if (actual > 0) quantile_ranks(actual, my_q, lo_i, hi_i);
+      klo = pref[tid];
+      khi = (hi_i == lo_i || (int64_t)cle[tid] >= lo_i + 2) ? klo : succ[tid];
+    }
+    auto key_at = [=](int64_t k) { return k == lo_i ? klo : khi; };
+    out[((int64_t)my_s * ngroups + g) * m + col] =
+        quantile_of_sorted<V>(key_at, len, actual, my_q, skipna);
+    if (out_count && my_s == 0) out_count[g * m + col] = actual;
+  }
+}
+
+template <typename V>
+int run_quantile_select_cols(fh_call* c, int nq) {
+  c->path_used = 3;
+  if (c->ngroups == 0 || c->m == 0) return 0;
+  auto kern = k_radixsel_cols<V>;
+  const int skipna = (c->flags & FH_SKIPNAN) ? 1 : 0;
+  /* more q than one launch has slots for: batches of pl.slots */
+  for (int b0 = 0; b0 < nq;) {
+    fh_selcols_plan pl;
+    if (!fh_selcols_plan_for(nq - b0, (int)sizeof(V), &pl)) return 22;
+    const int nb = std::min(nq - b0, pl.slots);
+    if (pl.lds_bytes > 64 * 1024)
+      FHQ_CHECK(hipFuncSetAttribute((const void*)kern,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)pl.lds_bytes));
+    const int64_t ntiles = (c->m + pl.C - 1) / pl.C;
+    /* one-dimensional grid, sliced in groups as launch_sortsel_cols does */
+    const int64_t gstep = std::max<int64_t>(1, (int64_t)0x7FFFFFFF / ntiles);
+    for (int64_t g0 = 0; g0 < c->ngroups; g0 += gstep) {
+      const int64_t ng = std::min<int64_t>(gstep, c->ngroups - g0);
+      hipLaunchKernelGGL(kern, dim3((unsigned)(ng * ntiles)), dim3(pl.block),
+                         (size_t)pl.lds_bytes, (hipStream_t)c->stream,
+                         (const V*)c->values, (const int32_t*)c->labels,
+                         (const int32_t*)c->perm, c->n, c->m, c->ldm, c->ngroups, g0,
+                         ntiles, pl.logC, c->means + b0, nb, skipna,
+                         (double*)c->out_sum + (int64_t)b0 * c->ngroups * c->m,
+                         b0 == 0 ? c->out_count : (int64_t*)nullptr);
+      FHQ_CHECK(hipGetLastError());
+    }
+    b0 += nb;
+  }
+  return 0;
+}
+
 template <typename V, typename L>
 int run_quantile(fh_call* c, const double* q_dev, int nq, double* out) {
   hipStream_t stream = (hipStream_t)c->stream;
@@ -566,6 +804,20 @@ int fh_grouped_quantile_cols(fh_call* c, int nq, int64_t max_seg_rows) {
     case FH_F64: return run_quantile_cols<double>(c, nq, max_seg_rows);
     case FH_I64: return run_quantile_cols<int64_t>(c, nq, max_seg_rows);
     case FH_I32: return run_quantile_cols<int32_t>(c, nq, max_seg_rows);
+    default: return 9;
+  }
+}
+
+/* column form for groups of any length (include/floxhip.h): radix selection */
+int fh_grouped_quantile_select_cols(fh_call* c, int nq) {
+  if (!c || !c->values || !c->labels || !c->perm || !c->out_sum || !c->means) return 22;
+  if (nq < 1) return 22;
+  if (c->n < 0 || c->m < 0 || c->ngroups < 0 || c->n >= (1LL << 31)) return 22;
+  switch (c->vdtype) {
+    case FH_F32: return run_quantile_select_cols<float>(c, nq);
+    case FH_F64: return run_quantile_select_cols<double>(c, nq);
+    case FH_I64: return run_quantile_select_cols<int64_t>(c, nq);
+    case FH_I32: return run_quantile_select_cols<int32_t>(c, nq);
     default: return 9;
   }
 }

@@ -40,6 +40,22 @@ Supported options:
       at any size, where the call is eligible: the conditions of
       cols_order_funcs, no hipGraph capture, and no group longer than the
       kernel's capacity (2048 rows) (core.py).
+  cols_select_funcs: False sends quantile/nanquantile/median/nanmedian over
+      leading dims through the lead fold as soon as one group is longer than
+      the sort-in-LDS capacity, with the fold's limit of N * lead_M < 2**31;
+      on (the default) such calls take the radix-select column kernel, which
+      finds each (group, column)'s order statistics in per-tile LDS digit
+      histograms: the caller's strided view is read in place (5 times for
+      4-byte values, 9 for 8-byte ones, one less where no column needs a
+      second key), at any size and any group length, where the call meets
+      the conditions of cols_sorted_funcs and lead_M >= cols_select_min_cols.
+      It extends cols_sorted_funcs and is off where that is off; mode and
+      nanmode keep the fold for long groups (core.py).
+  cols_select_min_cols: the narrowest lead_M that takes the radix-select
+      kernel. Its grid is column tiles x groups, so a narrow array with few
+      long groups is left to the fold; None = the measured default, 16384
+      (profiles/r11_cols_select.md). One column tile (64) is the least
+      useful value.
   cols_scan: False sends cumsum/nancumsum/ffill/bfill over leading dims
       through the lead fold (a flattened copy, composite int64 labels and a
       device-wide radix sort of N * lead_M pairs with about 70 B of scratch
@@ -74,6 +90,8 @@ OPTIONS = {
     "fused_many": None,               # None = on
     "cols_order_funcs": None,         # None = on
     "cols_sorted_funcs": None,        # None = on
+    "cols_select_funcs": None,        # None = on
+    "cols_select_min_cols": None,     # None = the measured default
     "cols_scan": None,                # None = on
     "cols_scan_min_cols": None,       # None = the measured default
 }
@@ -124,6 +142,16 @@ def _apply(name, value):
         if value is not None:
             core.COLS_SORTED_FUNCS = bool(value)
         return ("cols_sorted_funcs", old)
+    if name == "cols_select_funcs":
+        old = core.COLS_SELECT_FUNCS
+        if value is not None:
+            core.COLS_SELECT_FUNCS = bool(value)
+        return ("cols_select_funcs", old)
+    if name == "cols_select_min_cols":
+        old = core.COLS_SELECT_MIN_COLS
+        if value is not None:
+            core.COLS_SELECT_MIN_COLS = int(value)
+        return ("cols_select_min_cols", old)
     if name == "cols_scan":
         old = scan.COLS_SCAN
         if value is not None:
@@ -166,6 +194,10 @@ def _restore(name, old):
         core.COLS_ORDER_FUNCS = old
     elif name == "cols_sorted_funcs":
         core.COLS_SORTED_FUNCS = old
+    elif name == "cols_select_funcs":
+        core.COLS_SELECT_FUNCS = old
+    elif name == "cols_select_min_cols":
+        core.COLS_SELECT_MIN_COLS = old
     elif name == "cols_scan":
         scan.COLS_SCAN = old
     elif name == "cols_scan_min_cols":

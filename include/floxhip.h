@@ -298,6 +298,24 @@ int fh_grouped_quantile_cols(fh_call* c, int nq, int64_t max_seg_rows);
  * dtype (2048 for all four); 0 for an unknown dtype */
 int64_t fh_quantile_cols_max_rows(int vdtype);
 
+/* the same quantiles for groups of any length, by radix selection: inputs,
+ * FH_SKIPNAN, `means` = device q (f64[nq]), out_sum = f64 [nq][ngroups][m]
+ * and the nullable out_count as fh_grouped_quantile_cols takes them, without
+ * max_seg_rows. One workgroup serves one group's rows for a tile of columns:
+ * it refines the order-preserving key of every wanted rank one 8-bit digit
+ * per read of the segment, most significant first, in per-column LDS
+ * histograms (include/floxhip_selcols.h has the tile plan), so there is no
+ * capacity, no scratch, no host sync and no limit on n * m; more q than one
+ * launch has slots for are served in batches. Results equal
+ * fh_grouped_quantile's and fh_grouped_quantile_cols' bit for bit (the same
+ * interpolation rule runs on the selected keys). nq >= 1: the mode is not
+ * served. path_used = 3. Errors (no launch, outputs untouched): 22 = a
+ * missing buffer (values, labels, perm, out_sum, means), nq < 1, or a
+ * negative / out-of-int32 extent (within this entry; fh_grouped_scan_cols
+ * gives the number its own meaning); 9 = unknown value dtype. Came without a
+ * new revision (fh_call is unchanged): a caller detects it by the symbol. */
+int fh_grouped_quantile_select_cols(fh_call* c, int nq);
+
 /* grouped scans over the leading axis of a multi-column array: the column
  * form of fh_grouped_scan, op as there (0 cumsum, 1 nancumsum, 2 ffill,
  * 3 bfill). Inputs as fh_grouped_reduce_cols: values n x m with row stride
@@ -358,7 +376,8 @@ int fh_version(void);
  * FH_SET_IDXMIN/IDXMAX, FH_SET_ARGMIN_COLS/ARGMAX_COLS and fh_cols_supports
  * came without a new revision (it stays 6: fh_call is unchanged): a caller
  * detects them by the fh_cols_supports symbol and its answer. Likewise
- * fh_grouped_quantile_cols and fh_grouped_scan_cols, each by its own symbol. */
+ * fh_grouped_quantile_cols, fh_grouped_scan_cols and
+ * fh_grouped_quantile_select_cols, each by its own symbol. */
 int fh_abi_revision(void);
 
 #ifdef __cplusplus
