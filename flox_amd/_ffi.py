@@ -175,6 +175,19 @@ def load_library():
             ctypes.POINTER(FhCall), ctypes.c_int,
         ]
         lib.fh_grouped_quantile_select_cols.restype = ctypes.c_int
+    # and the row form of the grouped scans
+    if hasattr(lib, "fh_grouped_scan_rows"):
+        lib.fh_grouped_scan_rows.argtypes = [
+            ctypes.POINTER(FhCall), ctypes.c_int, ctypes.c_int64,
+        ]
+        lib.fh_grouped_scan_rows.restype = ctypes.c_int
+        lib.fh_scan_rows_max_groups.argtypes = [ctypes.c_int]
+        lib.fh_scan_rows_max_groups.restype = ctypes.c_int64
+        lib.fh_scan_rows_plan.argtypes = [
+            ctypes.c_int, ctypes.c_int64,
+            ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+        ]
+        lib.fh_scan_rows_plan.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -187,6 +200,30 @@ def has_select_cols() -> bool:
 def has_scan_cols() -> bool:
     """Whether the loaded library has fh_grouped_scan_cols."""
     return hasattr(load_library(), "fh_grouped_scan_cols")
+
+
+def has_scan_rows() -> bool:
+    """Whether the loaded library has fh_grouped_scan_rows."""
+    return hasattr(load_library(), "fh_grouped_scan_rows")
+
+
+def scan_rows_max_groups(vdtype: int) -> int:
+    """The largest group count fh_grouped_scan_rows serves for this value
+    dtype; 0 where the loaded library predates the entry."""
+    lib = load_library()
+    if not hasattr(lib, "fh_grouped_scan_rows"):
+        return 0
+    return int(lib.fh_scan_rows_max_groups(vdtype))
+
+
+def scan_rows_plan(vdtype: int, ngroups: int) -> tuple[int, int]:
+    """(lead rows per workgroup, time steps per tile) of fh_grouped_scan_rows
+    for this value dtype and group count."""
+    lib = load_library()
+    r, t = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib.fh_scan_rows_plan(vdtype, ngroups, ctypes.byref(r), ctypes.byref(t)),
+          _SCAN_ROWS_ERRORS)
+    return r.value, t.value
 
 
 def quantile_cols_max_rows(vdtype: int) -> int:
@@ -229,6 +266,18 @@ _QCOLS_ERRORS = {
 _SELECT_COLS_ERRORS = {
     22: "fh_grouped_quantile_select_cols: missing values/labels/perm/out_sum/q "
         "buffer, nq below 1, or an extent that is negative or beyond int32 rows",
+}
+
+
+# fh_grouped_scan_rows numbers its refusals as fh_grouped_scan_cols does
+_SCAN_ROWS_ERRORS = {
+    22: "fh_grouped_scan_rows: missing values/labels/out_sum buffer",
+    23: "fh_grouped_scan_rows: an extent that is negative, beyond int32 time "
+        "steps, or a row stride below the number of time steps",
+    24: "fh_grouped_scan_rows: unknown op, or a value dtype the op is not "
+        "served for (sums: f32/f64/i64, fills: f32/f64)",
+    25: "fh_grouped_scan_rows: ngroups exceeds fh_scan_rows_max_groups for the "
+        "value dtype",
 }
 
 

@@ -925,6 +925,61 @@ def grouped_scan_cols(
     return out
 
 
+def grouped_scan_rows(
+    values2d: torch.Tensor,
+    codes: torch.Tensor,
+    ngroups: int,
+    func: str,
+    out: torch.Tensor | None = None,
+) -> torch.Tensor:
+    """Grouped scan along the LAST axis of a 2-D array (m, n) whose last axis
+    has stride 1 (fh_grouped_scan_rows): cumsum / nancumsum for f32, f64 and
+    i64, ffill / bfill for f32 and f64. codes: int32 tensor of n group codes in
+    [-1, ngroups), in the original time order: nothing is sorted. Every
+    distinct code scans as one group per row, -1 included. The values are read
+    in place (row stride values2d.stride(0)) and the result is written once:
+    `out`, where given, is an (m, n) tensor of the values' dtype with unit
+    stride along n and any row stride, not overlapping the values; else a
+    contiguous one is allocated. No host sync: the call can be captured.
+    Returns the (m, n) result."""
+    lib = _ffi.load_library()
+    if not hasattr(lib, "fh_grouped_scan_rows"):
+        raise RuntimeError("libfloxhip.so lacks fh_grouped_scan_rows: rebuild the extension")
+    _require_gpu_tensor(values2d, "values")
+    assert values2d.ndim == 2 and (values2d.stride(1) == 1 or values2d.shape[1] <= 1)
+    assert codes.dtype == torch.int32 and codes.ndim == 1
+    if values2d.dtype not in _TORCH_VDTYPE:
+        raise NotImplementedError(f"engine=hip does not support values dtype {values2d.dtype}")
+    m, n = values2d.shape
+    assert codes.numel() == n
+    dev = values2d.device
+    if out is None:
+        out = torch.empty((m, n), dtype=values2d.dtype, device=dev)
+    assert out.shape == values2d.shape and out.dtype == values2d.dtype and out.device == dev
+    assert out.stride(1) == 1 or n <= 1
+
+    c = FhCall()
+    c.vdtype = _TORCH_VDTYPE[values2d.dtype]
+    c.ldtype = _ffi.L_I32
+    c.n = n
+    c.m = m
+    c.ngroups = ngroups
+    c.ldm = values2d.stride(0) if m > 1 else n
+    c.values = values2d.data_ptr()
+    codes = codes.contiguous()
+    c.labels = codes.data_ptr()
+    c.out_sum = out.data_ptr()
+    c.stream = torch.cuda.current_stream(dev).cuda_stream
+    _ffi.check(
+        lib.fh_grouped_scan_rows(
+            ctypes.byref(c), _SCAN_COLS_OPS[func], out.stride(0) if m > 1 else n),
+        _ffi._SCAN_ROWS_ERRORS,
+    )
+    for t in (values2d, codes, out):
+        _record(t, torch.cuda.current_stream(dev))
+    return out
+
+
 def var_partials(
     group_idx, array, *, skipnan, size, labels2=None, grp_shape=None,
     global_counts=None, global_sums=None,

@@ -20,6 +20,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/floxhip.h"
+#include "../../include/floxhip_scanrows.h"
 
 #define FHS_CHECK(x)                             \
   do {                                           \
@@ -379,6 +380,230 @@ int dispatch_scan_cols(fh_call* c, int op, int64_t ldo) {
   return 24;
 }
 
+/* ---- row form: grouped scans along the contiguous axis of an (m x n) array --
+ * The (lead_M, N) layout with the grouped (time) axis last: values[r * ldm + t].
+ * A single-wave workgroup owns R lead rows and walks the time axis in tiles of
+ * T steps (include/floxhip_scanrows.h has the plan and the LDS layout). Per
+ * tile: the R x T values come in coalesced along t (16 lanes x 16 B cover one
+ * row's 256 B; element-wise where a base or a stride breaks the alignment) and
+ * are laid out [t][R + 1] in LDS; the tile's T codes are staged once; lane r
+ * walks the T steps of row r in time order and overwrites the tile with the
+ * results; the tile goes out coalesced along t. The code at a step is the same
+ * for every row, so the walk's branches are wave-uniform: a lane keeps the
+ * running value of the current group in a register and, where the code
+ * changes, parks it at carry[slot * R + r] and fetches the new group's (slot =
+ * code + 1, the -1 steps being a group of their own). Lane r owns row r for
+ * the whole kernel, so its state lives in registers across tiles. Where a
+ * group starts is the same for every row too: s_first[slot] takes the walk
+ * position of the group's first step (an LDS atomicMin per staged code), and a
+ * step that finds its own position there starts its group, which is what lets
+ * a sum's first row initialise it and leaves the carries uninitialised. The
+ * vector form holds the next tile's loads in registers across the walk. bfill
+ * is ffill with tiles and steps walked from the last time step. */
+template <typename V, int OP, int R, bool VEC>
+__launch_bounds__(FH_SCANROWS_BLOCK) __global__ void k_scan_rows(
+    const V* __restrict__ values, const int* __restrict__ labels, int64_t m, int n,
+    int64_t ldm, int64_t ldo, int ngroups, V* __restrict__ out) {
+  constexpr bool REV = OP == SCAN_BFILL;
+  constexpr int T = FH_SCANROWS_TILE_BYTES / (int)sizeof(V);
+  constexpr int P = R + 1;                /* LDS pitch of one time step */
+  constexpr int VL = 16 / (int)sizeof(V); /* values per 16-B vector */
+  constexpr int NL = R / 4;               /* vectors per lane per tile: 4 rows per instruction */
+  constexpr int WU = 8;                   /* steps read before the first is consumed */
+  static_assert(T <= FH_SCANROWS_BLOCK, "one staged code per lane");
+  extern __shared__ __align__(16) unsigned char s_raw[];
+  V* s_carry = reinterpret_cast<V*>(s_raw);
+  V* s_tile = s_carry + (ngroups + 1) * R;
+  int* s_code = reinterpret_cast<int*>(s_tile + T * P);
+  int* s_first = s_code + T;
+
+  const int lane = threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.x * R;
+  const int vrow = lane / 16;         /* vector form: row within a group of 4 */
+  const int vt = (lane % 16) * VL;    /* and first step of this lane's vector */
+  const int ntiles = (n + T - 1) / T;
+
+  for (int i = lane; i <= ngroups; i += FH_SCANROWS_BLOCK) s_first[i] = INT32_MAX;
+
+  ScanVec<V, VL> x[NL];
+  int code_next = -1;
+  auto fetch = [&](int tt) {
+    const int t0 = (REV ? ntiles - 1 - tt : tt) * T;
+    const int nt = n - t0 < T ? n - t0 : T;
+    if (lane < nt) code_next = labels[t0 + lane];
+    if (!VEC) return;
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      const int r = j * 4 + vrow;
+#pragma unroll
+      for (int k = 0; k < VL; ++k) x[j].v[k] = (V)0;
+      if (r0 + r >= m) continue;
+      const V* src = values + (r0 + r) * ldm + t0 + vt;
+      if (vt + VL <= nt) {
+        x[j] = *reinterpret_cast<const ScanVec<V, VL>*>(src);
+      } else {
+#pragma unroll
+        for (int k = 0; k < VL; ++k)
+          if (vt + k < nt) x[j].v[k] = src[k];
+      }
+    }
+  };
+  if (ntiles > 0) fetch(0);
+
+  int cur = -1; /* no slot: slots are >= 0 */
+  V acc = (V)0;
+  for (int tt = 0; tt < ntiles; ++tt) {
+    const int t0 = (REV ? ntiles - 1 - tt : tt) * T;
+    const int nt = n - t0 < T ? n - t0 : T;
+    __syncthreads(); /* the previous tile is out; s_first is initialised */
+    if (VEC) {
+#pragma unroll
+      for (int j = 0; j < NL; ++j)
+#pragma unroll
+        for (int k = 0; k < VL; ++k) s_tile[(vt + k) * P + j * 4 + vrow] = x[j].v[k];
+    } else {
+#pragma unroll 8
+      for (int e = lane; e < R * T; e += FH_SCANROWS_BLOCK) {
+        const int r = e / T, t = e % T;
+        if (r0 + r < m && t < nt) s_tile[t * P + r] = values[(r0 + r) * ldm + t0 + t];
+      }
+    }
+    int slot = 0, w = 0;
+    if (lane < nt) {
+      /* a code outside [-1, ngroups) breaks the contract; it joins the -1 group
+       * instead of indexing past the carries */
+      slot = (code_next < 0 || code_next >= ngroups) ? 0 : code_next + 1;
+      w = REV ? n - 1 - (t0 + lane) : t0 + lane;
+      atomicMin(&s_first[slot], w);
+    }
+    __syncthreads();
+    if (lane < nt) s_code[lane] = slot | (s_first[slot] == w ? INT32_MIN : 0);
+    if (tt + 1 < ntiles) fetch(tt + 1);
+    __syncthreads();
+
+    if (lane < R) {
+      for (int i0 = 0; i0 < nt; i0 += WU) {
+        V xv[WU];
+        int pc[WU];
+#pragma unroll
+        for (int u = 0; u < WU; ++u) {
+          if (i0 + u >= nt) break;
+          const int idx = REV ? nt - 1 - (i0 + u) : i0 + u;
+          xv[u] = s_tile[idx * P + lane];
+          pc[u] = s_code[idx];
+        }
+#pragma unroll
+        for (int u = 0; u < WU; ++u) {
+          if (i0 + u >= nt) break;
+          const int p = __builtin_amdgcn_readfirstlane(pc[u]);
+          const int sl = p & INT32_MAX;
+          const bool first = p < 0;
+          if (sl != cur) {
+            if (cur >= 0) s_carry[cur * R + lane] = acc;
+            if (!first) acc = s_carry[sl * R + lane];
+            cur = sl;
+          }
+          acc = scan_step<V, OP>(acc, xv[u], first);
+          xv[u] = acc;
+        }
+#pragma unroll
+        for (int u = 0; u < WU; ++u) {
+          if (i0 + u >= nt) break;
+          const int idx = REV ? nt - 1 - (i0 + u) : i0 + u;
+          s_tile[idx * P + lane] = xv[u];
+        }
+      }
+    }
+    __syncthreads();
+
+    if (VEC) {
+#pragma unroll
+      for (int j = 0; j < NL; ++j) {
+        const int r = j * 4 + vrow;
+        if (r0 + r >= m) continue;
+        ScanVec<V, VL> y;
+#pragma unroll
+        for (int k = 0; k < VL; ++k) y.v[k] = s_tile[(vt + k) * P + r];
+        V* dst = out + (r0 + r) * ldo + t0 + vt;
+        if (vt + VL <= nt) {
+          *reinterpret_cast<ScanVec<V, VL>*>(dst) = y;
+        } else {
+#pragma unroll
+          for (int k = 0; k < VL; ++k)
+            if (vt + k < nt) dst[k] = y.v[k];
+        }
+      }
+    } else {
+#pragma unroll 8
+      for (int e = lane; e < R * T; e += FH_SCANROWS_BLOCK) {
+        const int r = e / T, t = e % T;
+        if (r0 + r < m && t < nt) out[(r0 + r) * ldo + t0 + t] = s_tile[t * P + r];
+      }
+    }
+  }
+}
+
+/* launcher of k_scan_rows: the vector form needs both row strides a multiple
+ * of the vector and both bases 16-B aligned (tiles start at multiples of 256
+ * B, so every vector of an aligned row is aligned). Dynamic LDS beyond 64 KiB
+ * needs the function attribute raised first. */
+template <typename V, int OP, int R>
+int launch_scan_rows_r(fh_call* c, int64_t ldo, const fh_scanrows_plan& pl) {
+  hipStream_t stream = (hipStream_t)c->stream;
+  constexpr int VL = 16 / (int)sizeof(V);
+  const bool vec = c->ldm % VL == 0 && ldo % VL == 0 && ((uintptr_t)c->values % 16) == 0 &&
+                   ((uintptr_t)c->out_sum % 16) == 0;
+  const int64_t nblk = (c->m + R - 1) / R;
+  if (nblk > INT32_MAX) return 23;
+  auto launch = [&](auto vecc) -> int {
+    auto kern = k_scan_rows<V, OP, R, decltype(vecc)::value>;
+    if (pl.lds_bytes > 64 * 1024)
+      FHS_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)pl.lds_bytes));
+    hipLaunchKernelGGL(kern, dim3((uint32_t)nblk), dim3(FH_SCANROWS_BLOCK),
+                       (size_t)pl.lds_bytes, stream, (const V*)c->values,
+                       (const int*)c->labels, c->m, (int)c->n, c->ldm, ldo, (int)c->ngroups,
+                       (V*)c->out_sum);
+    FHS_CHECK(hipGetLastError());
+    return 0;
+  };
+  const int rc = vec ? launch(std::true_type{}) : launch(std::false_type{});
+  if (rc) return rc;
+  c->path_used = 3;
+  return 0;
+}
+
+template <typename V, int OP>
+int launch_scan_rows(fh_call* c, int64_t ldo) {
+  fh_scanrows_plan pl;
+  if (!fh_scanrows_plan_for((int)sizeof(V), c->ngroups, &pl)) return 25;
+  switch (pl.R) {
+    case 64: return launch_scan_rows_r<V, OP, 64>(c, ldo, pl);
+    case 32: return launch_scan_rows_r<V, OP, 32>(c, ldo, pl);
+    default: return launch_scan_rows_r<V, OP, 16>(c, ldo, pl);
+  }
+}
+
+/* sums for f32/f64/i64, fills for f32/f64 */
+template <typename V>
+int dispatch_scan_rows(fh_call* c, int op, int64_t ldo) {
+  switch (op) {
+    case SCAN_CUMSUM: return launch_scan_rows<V, SCAN_CUMSUM>(c, ldo);
+    case SCAN_NANCUMSUM: return launch_scan_rows<V, SCAN_NANCUMSUM>(c, ldo);
+    default: break;
+  }
+  if constexpr (!std::is_same<V, int64_t>::value) {
+    if (op == SCAN_FFILL) return launch_scan_rows<V, SCAN_FFILL>(c, ldo);
+    if (op == SCAN_BFILL) return launch_scan_rows<V, SCAN_BFILL>(c, ldo);
+  }
+  return 24;
+}
+
+int scan_rows_value_bytes(int vdtype) {
+  return vdtype == FH_F32 ? 4 : (vdtype == FH_F64 || vdtype == FH_I64) ? 8 : 0;
+}
+
 template <typename V, typename L>
 int dispatch_scan_op(fh_call* c, int op, V* out) {
   switch (op) {
@@ -459,6 +684,45 @@ int fh_grouped_scan_cols(fh_call* c, int op, int64_t ldo) {
     case FH_F64: return dispatch_scan_cols<double>(c, op, ldo);
     default: return dispatch_scan_cols<int64_t>(c, op, ldo);
   }
+}
+
+/* grouped scan along the contiguous axis of an (m x n) array, in place on the
+ * caller's strided rows (include/floxhip.h has the contract). No scratch, no
+ * host sync, no chunk plan; every refusal returns before any launch. */
+int fh_grouped_scan_rows(fh_call* c, int op, int64_t ldo) {
+  if (!c || !c->values || !c->labels || !c->out_sum) return 22;
+  /* a single row has no stride to speak of */
+  if (c->n < 0 || c->m < 0 || c->ngroups < 0 || c->n > INT32_MAX ||
+      (c->m > 1 && (c->ldm < c->n || ldo < c->n)))
+    return 23;
+  if (op < SCAN_CUMSUM || op > SCAN_BFILL) return 24;
+  if (c->vdtype != FH_F32 && c->vdtype != FH_F64 && c->vdtype != FH_I64) return 24;
+  if (c->vdtype == FH_I64 && op >= SCAN_FFILL) return 24;
+  if (c->ngroups > fh_scanrows_max_groups(scan_rows_value_bytes(c->vdtype))) return 25;
+  if (c->n == 0 || c->m == 0) {
+    c->path_used = 3;
+    return 0;
+  }
+  switch (c->vdtype) {
+    case FH_F32: return dispatch_scan_rows<float>(c, op, ldo);
+    case FH_F64: return dispatch_scan_rows<double>(c, op, ldo);
+    default: return dispatch_scan_rows<int64_t>(c, op, ldo);
+  }
+}
+
+int64_t fh_scan_rows_max_groups(int vdtype) {
+  return fh_scanrows_max_groups(scan_rows_value_bytes(vdtype));
+}
+
+int fh_scan_rows_plan(int vdtype, int64_t ngroups, int* row_tile, int* time_tile) {
+  const int vb = scan_rows_value_bytes(vdtype);
+  if (!vb) return 24;
+  if (ngroups < 0) return 23;
+  fh_scanrows_plan pl;
+  if (!fh_scanrows_plan_for(vb, ngroups, &pl)) return 25;
+  if (row_tile) *row_tile = pl.R;
+  if (time_tile) *time_tile = pl.T;
+  return 0;
 }
 
 }  /* extern "C" */

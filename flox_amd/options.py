@@ -72,6 +72,24 @@ Supported options:
       parallelism is column tiles times group-aligned row chunks, so a
       narrow array with few long groups is left to the fold; None = the
       measured default (profiles/r10_cols_scan.md).
+  rows_scan: False sends the same four scans over leading dims through the
+      lead fold also where the grouped axis is the last, contiguous one (the
+      C-contiguous (lead..., N) layout every numpy input has on the device),
+      with the fold's sort, scratch and N * lead_M < 2**32 limit; on (the
+      default) the row kernel stages tiles of the caller's rows through LDS,
+      one lane per lead row walking the time steps in order with the other
+      groups' running values parked in LDS, reading the array in place and
+      writing the result once, at any size, where the call is eligible: the
+      column form does not apply, the (lead_M, N) view has unit stride along
+      N and one row stride without a copy, f32/f64/i64 values after promotion
+      for the sums and f32/f64 for the fills, not distributed, no datetime
+      values, 1 <= N < 2**31, no more groups than the kernel has LDS for
+      (2333 for 4-byte values, 1202 for 8-byte ones), and lead_M >=
+      rows_scan_min_rows. hipGraph capture does not exclude it (scan.py).
+  rows_scan_min_rows: the fewest lead rows that take the row form. Its
+      parallelism is lead rows alone, one wave per tile of up to 64 rows, so
+      an array with few rows is left to the fold; None = the measured
+      default (profiles/r12_rows_scan.md).
 """
 
 from __future__ import annotations
@@ -94,6 +112,8 @@ OPTIONS = {
     "cols_select_min_cols": None,     # None = the measured default
     "cols_scan": None,                # None = on
     "cols_scan_min_cols": None,       # None = the measured default
+    "rows_scan": None,                # None = on
+    "rows_scan_min_rows": None,       # None = the measured default
 }
 
 _CACHE_FIELDS = {
@@ -162,6 +182,16 @@ def _apply(name, value):
         if value is not None:
             scan.COLS_SCAN_MIN_COLS = int(value)
         return ("cols_scan_min_cols", old)
+    if name == "rows_scan":
+        old = scan.ROWS_SCAN
+        if value is not None:
+            scan.ROWS_SCAN = bool(value)
+        return ("rows_scan", old)
+    if name == "rows_scan_min_rows":
+        old = scan.ROWS_SCAN_MIN_ROWS
+        if value is not None:
+            scan.ROWS_SCAN_MIN_ROWS = int(value)
+        return ("rows_scan_min_rows", old)
     if name == "sparse_combine_ngroups":
         old = distributed.SPARSE_NGROUPS
         if value is not None:
@@ -202,6 +232,10 @@ def _restore(name, old):
         scan.COLS_SCAN = old
     elif name == "cols_scan_min_cols":
         scan.COLS_SCAN_MIN_COLS = old
+    elif name == "rows_scan":
+        scan.ROWS_SCAN = old
+    elif name == "rows_scan_min_rows":
+        scan.ROWS_SCAN_MIN_ROWS = old
     elif name == "sparse_combine_ngroups":
         distributed.SPARSE_NGROUPS = old
     elif name == "sparse_combine_fraction":

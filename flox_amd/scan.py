@@ -227,6 +227,22 @@ def groupby_scan(
                 .movedim(tuple(range(len(by_shape))),
                          tuple(range(arr.ndim - len(by_shape), arr.ndim)))
             )
+    if out is None and lead_M > 1:
+        rv = _rows_view(arr, len(by_shape), lead_M)
+        if _rows_scan_ok(func, rv, lead_M, ngroups, dt_dtype,
+                         distributed_combine and distributed.is_active()):
+            # the row form, for the grouped axis last and contiguous: tiles
+            # staged through LDS, one lane per lead row, codes in the caller's
+            # time order. No copy, no composite labels, no sort, no scratch,
+            # no host sync, no limit on N * lead_M.
+            from .aggregate_hip import grouped_scan_rows
+            from .core import _bounded_codes
+
+            codes = _bounded_codes(labels, labels2, grp_pair, ngroups).to(torch.int32)
+            out_full = torch.empty_like(arr)
+            out_rv = _rows_view(out_full, len(by_shape), lead_M)
+            res = grouped_scan_rows(rv, codes, ngroups, func, out=out_rv)
+            out = out_full if out_rv is not None else res.reshape(orig_shape)
     if out is None:
         out = _scan_fold(arr, func, lead_M, labels, labels2, grp_pair, ngroups,
                          distributed_combine, device).reshape(orig_shape)
@@ -290,6 +306,62 @@ def _cols_scan_ok(func, vt, lead_M, dt_dtype, dist_on):
         and not torch.cuda.is_current_stream_capturing()
         and _ffi.has_scan_cols()
     )
+
+
+# options.rows_scan: scans over leading dims of an array whose grouped axis is
+# last and contiguous (the C-contiguous (lead..., N) layout) take the row
+# kernel (fh_grouped_scan_rows) where the call is eligible (_rows_scan_ok)
+# instead of the lead fold. The column form is tried first.
+ROWS_SCAN = True
+# options.rows_scan_min_rows: the fewest lead rows that take it. A workgroup is
+# one wave that walks a tile of up to 64 rows, so a short array leaves most of
+# the chip idle. Measured at 2^26 elements, f32 and f64, cumsum and ffill, 2
+# groups in long runs and 24 cyclic groups (profiles/r12_rows_scan.md): at
+# 1024 rows the row form loses everywhere (1.6x to 2.5x the fold's time), at
+# 4096 it wins everywhere (0.41 to 0.64 of it), the smallest width of the
+# sweep where it loses in neither pattern for either dtype. Never below the
+# plan's largest row tile (64).
+ROWS_SCAN_MIN_ROWS = 4096
+
+
+def _rows_view(arr, nbydims, lead_M):
+    """The (lead_M, N) view of arr with the grouped dims last, or None where it
+    has no unit stride along N and one uniform row stride without a copy. A
+    row stride above N (a slice of wider storage) is fine."""
+    N = arr.numel() // lead_M
+    try:
+        rv = arr.view((lead_M, N))
+    except RuntimeError:
+        return None
+    if N > 1 and rv.stride(1) != 1:
+        return None
+    if lead_M > 1 and rv.stride(0) < N:
+        return None
+    return rv
+
+
+def _rows_scan_ok(func, rv, lead_M, ngroups, dt_dtype, dist_on):
+    """Whether a scan over leading dims takes the row form; rv is _rows_view's
+    answer. The entry makes no host sync, so a capturing stream is no
+    obstacle. Everything else keeps the lead fold with its results and
+    exceptions."""
+    if not (
+        ROWS_SCAN
+        and rv is not None
+        and lead_M > 1
+        and lead_M >= ROWS_SCAN_MIN_ROWS
+        and rv.dtype in (
+            (torch.float32, torch.float64, torch.int64)
+            if func in ("cumsum", "nancumsum") else (torch.float32, torch.float64)
+        )
+        and not dist_on
+        and dt_dtype is None
+        and 1 <= rv.shape[1] < 2**31
+        and _ffi.has_scan_rows()
+    ):
+        return False
+    vd = {torch.float32: _ffi.F32, torch.float64: _ffi.F64, torch.int64: _ffi.I64}[rv.dtype]
+    return ngroups <= _ffi.scan_rows_max_groups(vd)
 
 
 def _scan_fold(arr, func, lead_M, labels, labels2, grp_pair, ngroups,

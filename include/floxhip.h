@@ -346,6 +346,37 @@ int fh_grouped_quantile_select_cols(fh_call* c, int nq);
  * caller detects it by the symbol. */
 int fh_grouped_scan_cols(fh_call* c, int op, int64_t ldo);
 
+/* the row form of the same scans, for the other layout: values m lead rows x
+ * n time steps with the grouped (time) axis the contiguous one, element
+ * (r, t) at values[r * ldm + t], ldm >= n. labels = int32 codes, n of them,
+ * in the caller's ORIGINAL time order, each in [-1, ngroups): no sort and no
+ * perm. ngroups is read: a row's running value of every group but the current
+ * one waits in LDS, (ngroups + 1) values per row, which bounds the group count
+ * (include/floxhip_scanrows.h has the tile plan; fh_scan_rows_max_groups
+ * answers for a dtype). out_sum receives value-dtype m x n with row stride
+ * ldo and must not overlap values. Per lead row the semantics are exactly
+ * fh_grouped_scan_cols': every distinct code is a group, the -1 steps one of
+ * them; sequential adds in the value dtype in time order, so results equal
+ * the column form's bit for bit on the same data. Served: sums for FH_F32 /
+ * FH_F64 / FH_I64, fills for FH_F32 / FH_F64. The values are read once and
+ * written once, in place: no scratch, no D2H copy, no stream synchronize and
+ * no chunk plan, so the entry can run on a stream under hipGraph capture; no
+ * limit on n * m (offsets are 64-bit; n itself fits int32). path_used = 3.
+ * Errors (no launch, outputs untouched), numbered as fh_grouped_scan_cols
+ * numbers them: 22 = a missing buffer (values, labels, out_sum); 23 = a
+ * negative extent, n beyond int32, or a row stride below n; 24 = an unknown
+ * op or a (dtype, op) pair that is not served; 25 = ngroups beyond
+ * fh_scan_rows_max_groups for the dtype. Came without a new revision (fh_call
+ * is unchanged): a caller detects it by the symbol. */
+int fh_grouped_scan_rows(fh_call* c, int op, int64_t ldo);
+/* the largest ngroups fh_grouped_scan_rows serves for a value dtype; 0 for a
+ * dtype it does not serve */
+int64_t fh_scan_rows_max_groups(int vdtype);
+/* the tile of that call: lead rows per workgroup and time steps per tile.
+ * Returns 0, or the code fh_grouped_scan_rows would refuse with (23 negative
+ * ngroups, 24 dtype, 25 capacity), the outputs untouched. */
+int fh_scan_rows_plan(int vdtype, int64_t ngroups, int* row_tile, int* time_tile);
+
 /* pack (order-preserving 32-bit value encoding, global row index) into one
  * int64 key per row, so that a grouped MIN over the keys is argmin/argmax
  * with np.argmin's first-occurrence tie-break (the packed form of the
@@ -376,8 +407,9 @@ int fh_version(void);
  * FH_SET_IDXMIN/IDXMAX, FH_SET_ARGMIN_COLS/ARGMAX_COLS and fh_cols_supports
  * came without a new revision (it stays 6: fh_call is unchanged): a caller
  * detects them by the fh_cols_supports symbol and its answer. Likewise
- * fh_grouped_quantile_cols, fh_grouped_scan_cols and
- * fh_grouped_quantile_select_cols, each by its own symbol. */
+ * fh_grouped_quantile_cols, fh_grouped_scan_cols,
+ * fh_grouped_quantile_select_cols and fh_grouped_scan_rows, each by its own
+ * symbol. */
 int fh_abi_revision(void);
 
 #ifdef __cplusplus
